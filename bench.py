@@ -14,6 +14,9 @@ Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on t
 stream; `cpu_baseline` is the CPU oracle (a scalar C restatement of the reference's loops,
 oracle/) timed on this box's host cores over a bounded sample of the same coefficients.
 Other kernels of the path: --workload convert:<src>:<dst> | png | mixed (configs[4]: JPEG / PNG / QOI)  (same JSON shape).
+A plain run sets up, warms up, times --steps steps and prints the line (cpu_baseline null, roofline.traffic replayed from
+profiles/).  --full adds what takes time of its own: the parity check of every workload against the oracle before timing,
+the live rocprofv3 traffic passes, cpu_baseline and the `also` lines.  --dump-outputs DIR writes the last timed step's outputs.
 Measurement knobs (environment): GAMUT_BENCH_CONVERT_GB (resident chunk of the convert workloads, default 128), GAMUT_BENCH_STEP_MS (every
 timed step on stderr), GAMUT_BENCH_BACKEND=gloo (the optional gather without RCCL), GAMUT_BENCH_NOCHECK (experiments with deliberately
 wrong kernels only: the line says so in config.parity_check).
@@ -58,7 +61,28 @@ def parse():
     ap.add_argument("--also-seconds", type=float, default=420.0, help="wall-clock budget of the `also` lines; what does not fit is reported as skipped")
     ap.add_argument("--gather", action="store_true", help="N > 1: also time an all_gather of output slices over RCCL (after the timed region; the only use of RCCL in this script)")
     ap.add_argument("--also-args", default="", help="N > 1 test aid: extra arguments for every `also` sub-run (e.g. a small geometry); implies the `also` lines at any --batch")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the parity check against the oracle before timing, "
+                    "the live rocprofv3 traffic passes, cpu_baseline and the `also` lines (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy, "
+                    "float32: whole arrays up to %d elements, else a fixed seeded sample of that many" % DUMP_ELEMENTS)
     return ap.parse_args()
+
+
+DUMP_ELEMENTS = 1 << 23        # float32 values per dumped array: 32 MiB, so the pixels and a status array stay under 64 MB
+
+
+def dump_outputs(d, arrays):
+    """Writes each (name, tensor) as d/<name>.npy in float32: the whole array when it has at most DUMP_ELEMENTS values, else the values
+    at DUMP_ELEMENTS sorted flat indices drawn from a fixed seed (the same positions in every run of the same arguments)."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        if t.dtype == torch.int16:                                 # (the uint16 pixel types arrive as int16 views)
+            t = t.to(torch.int32) & 0xFFFF
+        if t.numel() > DUMP_ELEMENTS:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_ELEMENTS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 def host_cores():
@@ -111,7 +135,9 @@ def live_traffic(kernel_substr, pmc_batch):
     for flag in ("--steps", "--warmup", "--batch", "--gpus", "--cpu-seconds"):       # replaced below
         while flag in inner:
             i = inner.index(flag); del inner[i:i + 2]
-    inner = [a for a in inner if a not in ("--no-cpu", "--gather")]
+    while "--dump-outputs" in inner:
+        i = inner.index("--dump-outputs"); del inner[i:i + 2]
+    inner = [a for a in inner if a not in ("--no-cpu", "--gather", "--full")]
     vals = {}
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="gamut_pmc_", dir="/tmp")
@@ -167,7 +193,7 @@ def also_lines(budget_s):
         if left < 20:
             res.append({"what": what, "workload": wl, "skipped": "the --also-seconds budget ran out"})
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-also"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--no-also"] + extra
         # every line takes its HBM traffic live, at its own timed batch (two rocprofv3 --pmc passes restricted to this library's kernels),
         # as long as the budget has room for the lines behind it; a line that replays a committed summary names the file.  The mixed
         # step is three kernels side by side: no single-kernel traffic figure
@@ -248,7 +274,7 @@ def also_lines_multi(args, rank, world, dist):
             continue
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(ctl[0]))
         env.pop("TORCHELASTIC_USE_AGENT_STORE", None)             # the sub-run's rank 0 hosts its own store (the launcher's agent store is on the parent's port)
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--workload", wl, "--steps", "20", "--warmup", "5", "--no-cpu", "--no-also",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--workload", wl, "--steps", "20", "--warmup", "5", "--full", "--no-cpu", "--no-also",
                "--no-traffic"] + extra + shlex.split(args.also_args)
         t0 = time.perf_counter()
         e = {"what": what, "workload": wl}
@@ -437,6 +463,7 @@ def main():
                 n += 1
             dt = time.perf_counter() - t0
             return n * w * h / dt / 1e6, f"{n} of the batch's {w}x{h} coefficient frames (with max_zag: the sparse Row!N / Col!N paths), coefficients -> pixels, single thread, {dt:.1f} s"
+        outputs = {"pixels": out}
         dtype = "int32"
     elif wl.startswith("convert:"):
         import oracle_lib as O
@@ -503,6 +530,7 @@ def main():
                 n += 1
             dt = time.perf_counter() - t0
             return n * rows * w / dt / 1e6, f"{n} x {rows} rows of {w} px, scanlinesConvert, single thread, {dt:.1f} s"
+        outputs = {"pixels": out.view({np.uint8: torch.uint8, np.uint16: torch.int16, np.float32: torch.float32}[O.PT_DTYPE[dt_]])}
         dtype = "f32"
     elif wl == "png" or wl.startswith("png:"):
         import oracle_lib as O
@@ -561,6 +589,7 @@ def main():
                 n += 1
             dt = time.perf_counter() - t0
             return n * w * h / dt / 1e6, f"{n} of the batch's {w}x{h} filtered streams, stbi__create_png_image_raw, single thread, {dt:.1f} s"
+        outputs = {"pixels": out, "status": status}
         dtype = "u8"
     elif wl == "mixed":
         # BASELINE.json configs[4] on one rank: image i of the batch is a JPEG (i % 3 == 0), a PNG (1) or a QOI file (2), all
@@ -678,11 +707,12 @@ def main():
                 n += 1
             dt = time.perf_counter() - t0
             return n * w * h / dt / 1e6, f"{n} images of the same three kinds in turn (coefficients / filtered stream / QOI file -> rgba8), single thread, {dt:.1f} s"
+        outputs = {"pixels": out, "png_status": status}
         dtype = "u8"
     else:
         raise SystemExit(f"unknown workload {wl}")
 
-    if check is not None:                                  # EVERY rank checks its own batch: no rank times unverified output
+    if check is not None and args.full:                    # EVERY rank checks its own batch: no rank times unverified output
         if not os.environ.get("GAMUT_BENCH_NOCHECK"):      # experiments with deliberately wrong kernels (tools/variant.sh) only
             check()
 
@@ -750,10 +780,13 @@ def main():
         except Exception as e:                                          # the headline number does not depend on it
             gather = {"error": repr(e)[:200]}
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+
     # N > 1: the other BASELINE.json configs on the same N ranks ("1 vs 8 GPUs", "sharded across 8 MI355X"), each as a sub-run of
     # this script per rank -- fresh HBM, its own parity check on every rank, its own gloo rendezvous on a port rank 0 picks
     also_multi = None
-    if world > 1 and wl == "jpeg" and not args.no_also and ((B == 1024 and not (args.width or args.height)) or args.also_args):
+    if world > 1 and wl == "jpeg" and args.full and not args.no_also and ((B == 1024 and not (args.width or args.height)) or args.also_args):
         del coeffs, out, zag
         torch.cuda.empty_cache()
         also_multi = also_lines_multi(args, rank, world, dist)
@@ -762,7 +795,7 @@ def main():
         avg_kernel_s = float(np.mean(kern_ms)) * 1e-3
         achieved = bytes_per_step / avg_kernel_s / 1e9
         traffic, traffic_src = None, None
-        if world == 1 and not args.no_traffic and wl != "mixed":
+        if world == 1 and args.full and not args.no_traffic and wl != "mixed":
             # the counters are taken on the launch that is TIMED: the same batch (round 4 took them at batch 64, where the PNG kernel's
             # second touch of a line still hit the L2: 1.05 x the algorithmic bytes there, 1.28 x at the timed 512).  convert: layers are
             # independent 268 MB streams read once -- two of them.
@@ -782,7 +815,8 @@ def main():
             "higher_is_better": True, "scaling": "strong" if (wl == "mixed" and args.batch == 1024 and args.total_images) else "weak", "vs_baseline": None,
             "dtype": dtype, "data": "synthetic",
             "config": dict({"workload": workload, "images_per_gpu_per_step": B, "sharding": "image-index, no collective",
-                            "parity_check": check_note.get("checked", "see check() of this workload" if not os.environ.get("GAMUT_BENCH_NOCHECK") else "SKIPPED (GAMUT_BENCH_NOCHECK)")},
+                            "parity_check": check_note.get("checked", "not run (bench.py --full checks against the oracle before timing)" if not args.full else
+                                                           "see check() of this workload" if not os.environ.get("GAMUT_BENCH_NOCHECK") else "SKIPPED (GAMUT_BENCH_NOCHECK)")},
                            **(zstat if wl.startswith("jpeg") else {})),
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
@@ -799,7 +833,7 @@ def main():
                 ms = float(np.mean([a.elapsed_time(b) for a, b in fmt_ev[k][-args.steps:]])) if fmt_ev[k] else 0.0
                 res["config"]["per_format"][k] = {"images": cnt, "ms": round(ms, 4), "Mpx/s": round(cnt * w * h / ms / 1e3, 1) if ms > 0 else None,
                                                  "GB/s": round(fmt_bytes[k] / ms / 1e6, 1) if ms > 0 else None}
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             # (i) one thread -- how the reference measures itself (examples/qoix/source/main.d:146-152); (ii) every host core, one
             # image per thread at a time (the oracle is C called through ctypes, which releases the GIL).  SURVEY.md 8d.
             v, sample = cpu_leg(args.cpu_seconds * 0.6)
@@ -815,7 +849,7 @@ def main():
                                                     "sample": f"the same loop on {ncores} threads at once, {dt:.1f} s"}
         else:
             res["cpu_baseline"] = None
-        if world == 1 and wl == "jpeg" and not args.no_also and B == 1024 and not (args.width or args.height):
+        if world == 1 and wl == "jpeg" and args.full and not args.no_also and B == 1024 and not (args.width or args.height):
             del coeffs, out, zag                                          # the sub-runs want the HBM
             torch.cuda.empty_cache()
             res["also"] = also_lines(args.also_seconds)

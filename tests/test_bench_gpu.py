@@ -23,7 +23,7 @@ def _run(cmd, env=None):
 
 
 def test_single_gpu_line(hip):
-    r = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "32", "--cpu-seconds", "1"])
+    r = _run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--batch", "32", "--cpu-seconds", "1"])
     assert "max_zag" in r["config"]["workload"], "the headline launch passes m_mcu_block_max_zag, as a decode does"
     assert KEYS <= set(r) and r["n_gpus"] == 1 and r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "Mpx/s"
     assert r["higher_is_better"] is True and r["scaling"] == "weak" and r["vs_baseline"] is None and r["data"] == "synthetic"
@@ -33,6 +33,29 @@ def test_single_gpu_line(hip):
     assert r["value"] > 0 and rf["achieved"] > 0
     cb = r["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0 and cb["sample"]
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(hip, tmp_path):
+    """A plain run times --steps steps and nothing else (no oracle check, no cpu_baseline, no `also` lines); --dump-outputs writes the
+    last step's pixels as float32: here a seeded sample (the batch is larger than the dump cap), every sampled value == the oracle's."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    import oracle_lib as O
+    from gamut_amd import synth
+    w, h, B = 320, 200, 40
+    r = _run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--batch", str(B), "--width", str(w), "--height", str(h),
+              "--dump-outputs", str(tmp_path)])
+    assert KEYS <= set(r) and r["steps"] == 4 and r["ms_per_step"] > 0 and r["cpu_baseline"] is None and "also" not in r
+    assert r["config"]["parity_check"].startswith("not run")
+    got = np.load(tmp_path / "pixels.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_ELEMENTS,) and B * h * w * 4 > bench.DUMP_ELEMENTS
+    idx = torch.randint(0, B * h * w * 4, (bench.DUMP_ELEMENTS,), generator=torch.Generator().manual_seed(0)).sort().values.numpy()
+    co = synth.jpeg_coeff_batch(B, w, h, torch.device("cuda", 0), seed=1)
+    zag = synth.jpeg_max_zag(co)
+    exp = np.stack([O.jpeg_reconstruct(w, h, 3, 4, co[i].cpu().numpy(), zag[i].cpu().numpy(), 4) for i in range(B)]).reshape(-1)
+    assert np.array_equal(got, exp[idx].astype(np.float32))
 
 
 def test_two_ranks_one_line(hip):
@@ -52,11 +75,13 @@ def test_self_launch_two_ranks(hip):
     assert r["n_gpus"] == 2 and r["scaling"] == "strong" and r["config"]["images_per_gpu_per_step"] == 7
 
 
-def test_eight_ranks_one_device_no_rccl(hip):
-    """The shape of the driver's 8-GPU run on a 1-GPU box: eight ranks (sharing the device here), control plane over gloo -- the
-    default path creates no RCCL communicator at all (the data path has no collective) -- and EVERY rank checks its own batch."""
-    r = _run([sys.executable, "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "16"])
-    assert KEYS <= set(r) and r["n_gpus"] == 8 and r["cpu_baseline"] is None and r["value"] > 0 and r["scaling"] == "weak"
+def test_three_ranks_one_device_no_rccl(hip):
+    """The shape of the driver's multi-GPU run (`torch.distributed.run ... bench.py --gpus N`) on a 1-GPU box: more ranks than devices,
+    sharing the device here, control plane over gloo -- the default path creates no RCCL communicator at all (the data path has no
+    collective) -- and EVERY rank checks its own batch.  Three ranks: with this test process, at most five processes hold the GPU."""
+    r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
+              "--master-port", "29543", "bench.py", "--full", "--gpus", "3", "--steps", "2", "--warmup", "1", "--batch", "16"])
+    assert KEYS <= set(r) and r["n_gpus"] == 3 and r["cpu_baseline"] is None and r["value"] > 0 and r["scaling"] == "weak"
     assert "all 16 images == oracle" in r["config"]["parity_check"] and "gather" not in r
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.count('init_process_group("gloo"') == 1 and 'init_process_group("nccl"' not in src, "RCCL only behind --gather (dist.new_group)"
@@ -64,8 +89,11 @@ def test_eight_ranks_one_device_no_rccl(hip):
 
 def test_two_ranks_carry_the_other_configs(hip):
     """N > 1: one command yields the "1 vs 8 GPUs" figures of configs 3 / 4 / 5 too -- every rank runs each workload as a sub-run with a
-    rendezvous of its own (small geometry here), rank 0 condenses the lines, a failure on any rank fails the line."""
-    r = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--also-args", "--width 320 --height 200"])
+    rendezvous of its own (small geometry here), rank 0 condenses the lines, a failure on any rank fails the line.  Launched as the driver
+    does: no self-launching parent, so two ranks and their two sub-run ranks are all that hold the GPU beside this process."""
+    r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+              "--master-port", "29545", "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16",
+              "--also-args", "--width 320 --height 200"])
     sys.path.insert(0, ROOT)
     import bench
     assert r["n_gpus"] == 2 and len(r["also"]) == len(bench.ALSO_MULTI)
@@ -77,7 +105,7 @@ def test_two_ranks_carry_the_other_configs(hip):
 
 def test_live_traffic_counters(hip):
     """roofline.traffic is measured in the run (rocprofv3 --pmc passes on this very workload), not replayed from a file"""
-    r = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "32", "--no-cpu"])
+    r = _run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--batch", "32", "--no-cpu"])
     rf = r["roofline"]
     if rf["traffic"] is None or "replayed" in (rf.get("traffic_source") or ""):
         pytest.skip(f"rocprofv3 counters unavailable here: {rf.get('traffic_source')}")
@@ -86,7 +114,7 @@ def test_live_traffic_counters(hip):
 
 def test_mixed_workload_line(hip):
     """BASELINE.json configs[4] on one rank: JPEG / PNG / QOI by image index, per-format breakdown, parity checked inside"""
-    r = _run([sys.executable, "bench.py", "--workload", "mixed", "--steps", "2", "--warmup", "1", "--batch", "7", "--width", "320", "--height", "200",
+    r = _run([sys.executable, "bench.py", "--full", "--workload", "mixed", "--steps", "2", "--warmup", "1", "--batch", "7", "--width", "320", "--height", "200",
               "--cpu-seconds", "1"])
     pf = r["config"]["per_format"]
     assert [pf[k]["images"] for k in ("jpeg", "png", "qoi")] == [3, 2, 2] and all(pf[k]["ms"] > 0 for k in pf)
@@ -99,7 +127,7 @@ def test_mixed_workload_line(hip):
 # the parity test at full size -- the launch shapes the small-geometry tests do not reach (512 x 4K takes the device-wide work
 # queue of k_png_defilter_queue, 256 layers are converted in resident chunks, 1024 mixed images put three formats side by side).
 def _stated(workload, *extra):
-    return _run([sys.executable, "bench.py", "--workload", workload, "--steps", "1", "--warmup", "1", "--no-cpu", "--no-traffic"] + list(extra))
+    return _run([sys.executable, "bench.py", "--full", "--workload", workload, "--steps", "1", "--warmup", "1", "--no-cpu", "--no-traffic"] + list(extra))
 
 
 def test_config2_with_max_zag_from_files(hip):
@@ -132,9 +160,9 @@ def test_config5_1024_mixed_images(hip):
     assert r["config"]["images_per_gpu_per_step"] == 1024 and [pf[k]["images"] for k in ("jpeg", "png", "qoi")] == [342, 341, 341]
 
 
-def test_default_line_carries_the_other_configs(hip):
-    """the driver's own `python bench.py` line: the headline + an `also` entry per other config, each with its parity verdict"""
-    r = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--cpu-seconds", "2", "--no-traffic", "--also-seconds", "400"])
+def test_full_line_carries_the_other_configs(hip):
+    """`python bench.py --full`: the headline + an `also` entry per other config, each with its parity verdict"""
+    r = _run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "2", "--no-traffic", "--also-seconds", "400"])
     sys.path.insert(0, ROOT)
     import bench
     n = len(bench.ALSO)                                                 # the other BASELINE.json configs (+ 4:4:4, -> rgb8, -> l8), inputs resident in HBM

@@ -288,13 +288,11 @@ def test_oracle_equals_reference_derived_jpeg_vectors():
     check_oracle_against_jpeg_vectors()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference tree (build container only)")
-def test_jpeg_vectors_and_generated_regions_are_current():
-    """the committed vectors are what the restatement produces now, and the restatement's generated regions are what
-    jpegload.d transliterates to now"""
+def test_jpeg_vectors_are_current():
+    """the committed vectors are what the restatement (tools/ref_literal_jpeg.py) produces now.  Whether the restatement's generated
+    regions are still what the reference's jpegload.d transliterates to needs that source: tools/make_ref_literal.py --check."""
     import subprocess, sys
     root = os.path.dirname(HERE)
-    subprocess.check_call([sys.executable, os.path.join(root, "tools", "make_ref_literal.py"), "--check"])
     subprocess.check_call([sys.executable, os.path.join(root, "tools", "make_jpeg_vectors.py"), "--check"])
 
 
@@ -321,14 +319,6 @@ def test_jpeg_literal_restatement_pixels_small_frames():
             crs = np.concatenate([sb[512 + ((row // 8) * 2 + k) * 64 + (row & 7) * 8:][:8] for row in range(16) for k in (0, 1)])
             assert np.array_equal(lines[:, 0], r[yy // 5, cbv, crs]) and np.array_equal(lines[:, 1], g[yy // 5, cbv, crs])
             assert np.array_equal(lines[:, 2], b[yy // 5, cbv, crs]) and (lines[:, 3] == 255).all()
-
-
-@pytest.mark.skipif(not os.path.exists("/root/reference/source/gamut/codecs/jpegload.d"), reason="reference tree not present")
-def test_jpeg_literal_restatement_is_current_transliteration():
-    """the P_Q / R_S and the Row / Col statements in tools/ref_literal_jpeg.py are exactly what tools/make_ref_literal.py produces
-    from the D text today"""
-    import subprocess, sys
-    subprocess.check_call([sys.executable, os.path.join(os.path.dirname(HERE), "tools", "make_ref_literal.py"), "--check"])
 
 
 def test_jpeg_rowcol_transliteration_equals_the_handwritten_reading():
@@ -513,25 +503,22 @@ def test_convert_matches_reference_vectors():
     check_convert_against_reference_vectors()
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/source/gamut/scanline.d"), reason="reference tree not present")
-def test_convert_vectors_are_current_and_random_sweep_vs_reference_text():
-    """the committed vectors are what the reference's text gives today, and on fresh random rows of every pair the oracle
-    equals the executed reference too (premultiplied, grey and float->int expressions included: scanline.d:240-803)"""
+def test_convert_random_sweep_vs_stored_reference_outputs():
+    """on a second set of random rows (seed 99) of every pair the oracle equals the executed reference too (premultiplied, grey and
+    float->int expressions included: scanline.d:240-803): tests/golden/scanline_sweep_sha.json holds the sha256 of the reference's
+    output row per pair, made with scanline_ref.npz by tools/make_scanline_vectors.py, which is also how both are re-checked against the
+    reference's source"""
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
     import make_scanline_vectors as M
-    fresh = M.build()
-    z, _ = _scanline_vectors()
-    assert set(fresh) == set(z.files)
-    for k in z.files:
-        assert np.array_equal(fresh[k], z[k]), k
-    R = M.Reference()
+    sha = json.load(open(os.path.join(G, "scanline_sweep_sha.json")))
     ins = M.inputs(np.random.default_rng(99))
+    assert len(sha) == len(PIXEL_TYPES) * (len(PIXEL_TYPES) - 1)
     for s in PIXEL_TYPES:
         for d in PIXEL_TYPES:
             if s != d:
-                exp = R.convert_row(s, d, ins[s], M.N, M.SIZE)
-                assert np.array_equal(O.scanlines_convert(s, ins[s], d, M.N, 1).view(np.uint8).reshape(-1), exp), (s, d)
+                got = O.scanlines_convert(s, ins[s], d, M.N, 1).view(np.uint8).reshape(-1)
+                assert hashlib.sha256(got.tobytes()).hexdigest() == sha[f"{s}_{d}"], (s, d)
 
 
 def test_convert_composite_tables():

@@ -547,7 +547,7 @@ def test_rccl_gather_two_ranks_through_the_c_abi(hip, tmp_path):
     import torch
     ndev = torch.cuda.device_count()
     if ndev < 2:
-        pytest.skip("RCCL refuses two ranks on one device; needs 2 GPUs (the driver's 8-GPU node)")
+        pytest.skip(f"needs 2 GPUs, found {ndev}: RCCL refuses two ranks on one device")
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     idfile = str(tmp_path / "rccl_id")

@@ -5,7 +5,7 @@ for rep in 1 2; do
 for v in ${VARIANTS:-prev base}; do
   if [ $v = base ]; then L=gamut_amd/lib/libgamut_hip.so; else L=gamut_amd/lib/var/libgamut_hip_$v.so; fi
   for wl in ${WLS:-jpeg:3 jpeg:1}; do
-    GAMUT_HIP_LIB=$L timeout 200 python bench.py --workload $wl --steps 20 --warmup 5 --no-cpu --no-also --no-traffic 2>&1 | python -c "
+    GAMUT_HIP_LIB=$L timeout 200 python bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu --no-also --no-traffic 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # Every bench.py workload once (same box, same build) -> gpurun_out/bench_matrix.jsonl; copy into profiles/ to commit.
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/bench_matrix.jsonl; mkdir -p $REPO/gpurun_out; : > $OUT
-run() { timeout 400 python $REPO/bench.py --no-cpu "$@" 2>/dev/null | tail -1 >> $OUT; }
+run() { timeout 400 python $REPO/bench.py --full --no-cpu "$@" 2>/dev/null | tail -1 >> $OUT; }
 run --workload jpeg
 for w in jpeg:3 jpeg:1; do run --workload $w; done
 for w in jpeg:4:1 jpeg:3:1 jpeg:4:2 jpeg:4:3 jpeg:3:3 jpeg:1:0; do run --workload $w --batch 512; done

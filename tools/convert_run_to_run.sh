@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-$(pwd)}; mkdir -p gpurun_out
 K=${1:-5}
 for p in $(seq 1 $K); do for w in convert:rgbaf32:rgba8 convert:rgba8:rgba16 convert:rgba16:rgba8 convert:rgba16:rgbaf32; do
-  timeout 300 python bench.py --workload $w --batch 64 --steps 10 --warmup 2 --no-cpu --no-traffic --no-also 2>&1 | python -c "
+  timeout 300 python bench.py --full --workload $w --batch 64 --steps 10 --warmup 2 --no-cpu --no-traffic --no-also 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

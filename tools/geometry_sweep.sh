@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out
 OUT=gpurun_out/${1:-r06_geometry_sweep.txt}; : > $OUT
 run() {  # workload width height batch
-  timeout 200 python bench.py --workload $1 --width $2 --height $3 --batch $4 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also 2>/dev/null | python -c "
+  timeout 200 python bench.py --full --workload $1 --width $2 --height $3 --batch $4 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ for rep in 1 2 3; do for v in jprev base; do
   if [ $v = base ]; then L=gamut_amd/lib/libgamut_hip.so; else L=gamut_amd/lib/var/libgamut_hip_$v.so; fi
   for spec in "jpeg 1080 1920 1024" "jpeg 1366 768 2048" "jpeg 1000 1000 2048" "jpeg 1920 1080 1024"; do
     set -- $spec
-    GAMUT_HIP_LIB=$L timeout 200 python bench.py --workload $1 --width $2 --height $3 --batch $4 --steps 20 --warmup 5 --no-cpu --no-traffic --no-also 2>&1 | python -c "
+    GAMUT_HIP_LIB=$L timeout 200 python bench.py --full --workload $1 --width $2 --height $3 --batch $4 --steps 20 --warmup 5 --no-cpu --no-traffic --no-also 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """make_scanline_vectors.py -- golden vectors for the PixelType conversion matrix, produced by EXECUTING the reference's own
 scanline functions (tools/d_scanline_exec.py transpiles source/gamut/scanline.d statement by statement; needs
-/root/reference, so it runs in the build container only).  Output: tests/golden/scanline_ref.npz
+the reference's source tree, so it runs where that is present).  Output: tests/golden/scanline_ref.npz and scanline_sweep_sha.json
 
     in_<type>            input pixels of one row (uint8 view), chosen per source type:
                            8-bit:   every value of a channel against every value of alpha (premultiplied types), ramps otherwise
@@ -98,8 +98,20 @@ def build():
     return arrays
 
 
+def sweep():
+    """a second input set, inputs(np.random.default_rng(99)), through every pair: {"<src>_<dst>": sha256 of the output row}
+    (tests/golden/scanline_sweep_sha.json; the inputs are regenerated from the seed, the outputs are too large to store)"""
+    R = Reference()
+    ins = inputs(np.random.default_rng(99))
+    return {f"{s}_{d}": hashlib.sha256(R.convert_row(s, d, ins[s], N, SIZE).tobytes()).hexdigest() for s in TYPES for d in TYPES if s != d}
+
+
 if __name__ == "__main__":
     arrays = build()
     path = os.path.join(ROOT, "tests", "golden", "scanline_ref.npz")
     np.savez_compressed(path, **arrays)
     print(path, os.path.getsize(path), "bytes,", len(arrays), "arrays")
+    path = os.path.join(ROOT, "tests", "golden", "scanline_sweep_sha.json")
+    with open(path, "w") as f:
+        json.dump(sweep(), f, indent=0, sort_keys=True)
+    print(path, os.path.getsize(path), "bytes")

@@ -14,9 +14,9 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python $REPO/bench.py "$@" --no-also > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python $REPO/bench.py --full "$@" --no-also > $OUT/bench.json 2> $OUT/bench.err
 tail -1 $OUT/bench.json
-timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace -o t -- python $REPO/bench.py "$@" --no-cpu --no-also --no-traffic > $OUT/trace.log 2>&1
+timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace -o t -- python $REPO/bench.py --full "$@" --no-cpu --no-also --no-traffic > $OUT/trace.log 2>&1
 GAMUT_BENCH_NOCHECK=1 timeout 400 rocprofv3 --output-format csv --kernel-include-regex gamut --pmc FETCH_SIZE -d $OUT/pmc_fetch -o t -- python $REPO/bench.py "$@" --steps 3 --warmup 1 --no-cpu --no-also --no-traffic --batch $PB > $OUT/pmc_fetch.log 2>&1
 GAMUT_BENCH_NOCHECK=1 timeout 400 rocprofv3 --output-format csv --kernel-include-regex gamut --pmc WRITE_SIZE -d $OUT/pmc_write -o t -- python $REPO/bench.py "$@" --steps 3 --warmup 1 --no-cpu --no-also --no-traffic --batch $PB > $OUT/pmc_write.log 2>&1
 grep "^{" $OUT/trace.log | tail -1 > $OUT/bench_profiled.json        # the line of the PROFILED run: its HIP-event average and rocprofv3's come from one process

@@ -3,6 +3,7 @@
 # Kernel statistics are those of the TIMED dispatches of each profiled bench.py run (tools/summarize_prof.py); the PMC passes run at a batch
 # that launches the kernel the bench times (PNG: 64 images = 2 176 (image, band) units: the work-queue kernel).
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT_DIR=${OUT_DIR:-$R/out}; mkdir -p $OUT_DIR     # the bench.py lines' outputs
 cd $R
 bash tools/profile.sh r04_jpeg 64 -- --steps 30 --warmup 10
 bash tools/profile.sh r04_jpeg_photo 64 -- --workload jpeg:photo --steps 30 --warmup 10
@@ -22,7 +23,7 @@ trace() {   # trace <tag> <timed dispatches per kernel> -- <command...>
    timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d /tmp/tr_$tag/trace -o t -- "$@" > $R/gpurun_out/summary_$tag/run.txt 2>&1;
    python $R/tools/summarize_prof.py /tmp/tr_$tag $R/gpurun_out/summary_$tag 0 $steps | head -12; rm -rf /tmp/tr_$tag)
 }
-trace r04_mixed_8192 10 -- python $R/bench.py --workload mixed --total-images 8192 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also
+trace r04_mixed_8192 10 -- python $R/bench.py --full --workload mixed --total-images 8192 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also
 trace r04_jpeg_files 0 -- python $R/tools/e2e_bench.py --batch 1024 --paths c --reps 4
 trace r04_progressive_files 0 -- python $R/tools/e2e_bench.py --batch 1024 --paths c --reps 2 --progressive
 trace r04_png_files 0 -- python $R/tools/e2e_png_bench.py --batch 256
@@ -38,4 +39,4 @@ bash tools/pmc_valu.sh > gpurun_out/summary_r04_pmc_valu.txt 2>&1
 for b in 256 1024 4096; do GAMUT_HIP_TRACE=1 timeout 300 python tools/e2e_bench.py --batch $b --paths c --reps 2 --progressive 2>&1 | grep -v "amdgpu" | tail -12; done > gpurun_out/r04_progressive_final.txt 2>&1
 (hipcc --offload-arch=gfx950 -O2 tools/microbench/chain_latency.hip -o /tmp/cl 2>/dev/null && timeout 60 /tmp/cl) > gpurun_out/r04_chain_latency.txt 2>&1
 (hipcc --offload-arch=gfx950 -O2 tools/microbench/h2d_streams.hip -o /tmp/h2d 2>/dev/null && timeout 120 /tmp/h2d) > gpurun_out/r04_h2d_streams.txt 2>&1
-(time python bench.py) > gpurun_out/r04_bench_default.log 2>&1
+(time python bench.py --full) > $OUT_DIR/r04_bench_default.log 2>&1

@@ -3,6 +3,7 @@
 # Kernel statistics are those of the TIMED dispatches of each profiled bench.py run (tools/summarize_prof.py); the PMC passes (FETCH_SIZE /
 # WRITE_SIZE) run at the TIMED batch of every workload (1024 JPEG images, 512 PNG images).
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT_DIR=${OUT_DIR:-$R/out}; mkdir -p $OUT_DIR     # the bench.py lines' outputs
 cd $R
 bash tools/profile.sh r05_jpeg 1024 -- --steps 30 --warmup 10
 bash tools/profile.sh r05_jpeg_photo 1024 -- --workload jpeg:photo --steps 30 --warmup 10
@@ -24,7 +25,7 @@ trace() {   # trace <tag> <timed dispatches per kernel> -- <command...>
    timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d /tmp/tr_$tag/trace -o t -- "$@" > $R/gpurun_out/summary_$tag/run.txt 2>&1;
    python $R/tools/summarize_prof.py /tmp/tr_$tag $R/gpurun_out/summary_$tag 0 $steps | head -12; rm -rf /tmp/tr_$tag)
 }
-trace r05_mixed_8192 10 -- python $R/bench.py --workload mixed --total-images 8192 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also
+trace r05_mixed_8192 10 -- python $R/bench.py --full --workload mixed --total-images 8192 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also
 trace r05_jpeg_files 0 -- python $R/tools/e2e_bench.py --batch 1024 --paths c --reps 4
 trace r05_progressive_files 0 -- python $R/tools/e2e_bench.py --batch 1024 --paths c --reps 2 --progressive
 trace r05_png_files 0 -- python $R/tools/e2e_png_bench.py --batch 256
@@ -32,4 +33,4 @@ trace r05_png_files 0 -- python $R/tools/e2e_png_bench.py --batch 256
 python tools/files_bench.py > gpurun_out/r05_files_bench.jsonl 2>/dev/null
 GAMUT_HIP_HOST_THREADS=2 python tools/files_bench.py > gpurun_out/r05_files_bench_2threads.jsonl 2>/dev/null
 python tools/e2e_mixed_bench.py --batch 768 > gpurun_out/r05_mixed_e2e.txt 2>&1; python tools/e2e_mixed_bench.py --batch 3072 >> gpurun_out/r05_mixed_e2e.txt 2>&1
-(time python bench.py) > gpurun_out/r05_bench_default.log 2>&1
+(time python bench.py --full) > $OUT_DIR/r05_bench_default.log 2>&1

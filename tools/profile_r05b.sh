@@ -2,6 +2,7 @@
 # Round 5's profile set, second half (the first half -- the JPEG workloads with their counters at batch 1024 -- ran from tools/profile_r05.sh before the
 # box's time limit): the PNG and convert workloads, the kernel traces of the mixed step and of the file-level calls, tools/files_bench.py, the default line.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT_DIR=${OUT_DIR:-$R/out}; mkdir -p $OUT_DIR     # the bench.py lines' outputs
 cd $R
 bash tools/profile.sh r05_png_random 512 -- --workload png --steps 10 --warmup 3
 bash tools/profile.sh r05_png 512 -- --workload png:heuristic --steps 10 --warmup 3
@@ -15,10 +16,10 @@ trace() {   # trace <tag> <timed dispatches per kernel> -- <command...>
    timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d /tmp/tr_$tag/trace -o t -- "$@" > $R/gpurun_out/summary_$tag/run.txt 2>&1;
    python $R/tools/summarize_prof.py /tmp/tr_$tag $R/gpurun_out/summary_$tag 0 $steps | head -12; rm -rf /tmp/tr_$tag)
 }
-trace r05_mixed_8192 10 -- python $R/bench.py --workload mixed --total-images 8192 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also
+trace r05_mixed_8192 10 -- python $R/bench.py --full --workload mixed --total-images 8192 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also
 trace r05_jpeg_files 0 -- python $R/tools/e2e_bench.py --batch 1024 --paths c --reps 4
 trace r05_progressive_files 0 -- python $R/tools/e2e_bench.py --batch 1024 --paths c --reps 2 --progressive
 trace r05_png_files 0 -- python $R/tools/e2e_png_bench.py --batch 256
 python tools/files_bench.py > gpurun_out/r05_files_bench.jsonl 2>/dev/null
 python tools/e2e_mixed_bench.py --batch 3072 > gpurun_out/r05_mixed_e2e.txt 2>&1
-(time python bench.py) > gpurun_out/r05_bench_default.log 2>&1
+(time python bench.py --full) > $OUT_DIR/r05_bench_default.log 2>&1

@@ -2,6 +2,7 @@
 # Round 6's profile set, on the GPU box:  bash tools/profile_r06.sh [a|b]   -> gpurun_out/summary_r06_*/ and gpurun_out/r06_*  (copied into profiles/)
 # Kernel statistics = the TIMED dispatches of each profiled bench.py run (tools/summarize_prof.py); counter passes at the TIMED batch.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT_DIR=${OUT_DIR:-$R/out}; mkdir -p $OUT_DIR     # the bench.py lines' outputs
 cd $R
 if [ "${1:-a}" = a ]; then
 bash tools/profile.sh r06_jpeg 1024 -- --steps 30 --warmup 10
@@ -22,8 +23,8 @@ trace() {   # trace <tag> <timed dispatches per kernel> -- <command...>
    timeout 400 rocprofv3 --output-format csv --kernel-trace --stats -d /tmp/tr_$tag/trace -o t -- "$@" > $R/gpurun_out/summary_$tag/run.txt 2>&1;
    python $R/tools/summarize_prof.py /tmp/tr_$tag $R/gpurun_out/summary_$tag 0 $steps | head -12; rm -rf /tmp/tr_$tag)
 }
-trace r06_mixed_8192 10 -- python $R/bench.py --workload mixed --total-images 8192 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also
+trace r06_mixed_8192 10 -- python $R/bench.py --full --workload mixed --total-images 8192 --steps 10 --warmup 3 --no-cpu --no-traffic --no-also
 python tools/files_bench.py > gpurun_out/r06_files_bench.jsonl 2>/dev/null
-(time python bench.py) > gpurun_out/r06_bench_default.log 2>&1
-GAMUT_BENCH_BACKEND=gloo python bench.py --gpus 8 --batch 16 --steps 3 --warmup 1 > gpurun_out/r06_bench_8ranks_one_device.json 2> gpurun_out/r06_bench_8ranks_one_device.err
+(time python bench.py --full) > $OUT_DIR/r06_bench_default.log 2>&1
+GAMUT_BENCH_BACKEND=gloo python bench.py --full --gpus 8 --batch 16 --steps 3 --warmup 1 > $OUT_DIR/r06_bench_8ranks_one_device.json 2> $OUT_DIR/r06_bench_8ranks_one_device.err
 fi
