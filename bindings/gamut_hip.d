@@ -132,6 +132,11 @@ extern(C)
     int   gamut_hip_qoi_decode_resident_device(const(ubyte)* blob, long blob_len, const(long)* begin, const(int)* size,
                                                const(gamut_hip_qoi_desc)* descs, int count, int channels,
                                                const(long)* out_offset, ubyte* out_, void* stream);
+    long  gamut_hip_qoi_encode_bound(const(gamut_hip_qoi_desc)* desc);
+    void* gamut_hip_qoi_encode(const(void)* data, const(gamut_hip_qoi_desc)* desc, int pitch_bytes, int* out_len);
+    int   gamut_hip_qoi_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(gamut_hip_qoi_desc)* descs,
+                                            int count, const(long)* out_offset, ubyte* out_, long* out_len,
+                                            int* status_host, void* stream);
 
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }

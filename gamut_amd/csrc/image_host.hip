@@ -598,6 +598,55 @@ int gamut_image_copy_pixels_to_host(gamut_image* img, int layer, void* dst, int6
     return 1;
 }
 
+// ---- saving (image.d:940-1011): saveToStream -> g_plugins[fif].saveProc; only saveQOI (plugins/qoi.d:149-184) has an encoder here ----
+uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980
+{
+    (void)flags;                                               // saveQOI ignores them
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data || fif != GAMUT_FORMAT_QOI) return nullptr;
+    gamut_hip_qoi_desc desc{};
+    desc.width = (uint32_t)img->_width; desc.height = (uint32_t)img->_height; desc.colorspace = 0;       // QOI_SRGB
+    if (img->_type == GAMUT_PIXEL_rgb8) desc.channels = 3;
+    else if (img->_type == GAMUT_PIXEL_rgba8) desc.channels = 4;
+    else return nullptr;
+    if (gamut_hip_qoi_encode_bound(&desc) == 0) return nullptr;                                         // what qoi_encode refuses
+    if (!img->_device) {                                       // host pixels: the drop-in stages them through pinned memory
+        int n = 0;
+        uint8_t* r = (uint8_t*)gamut_hip_qoi_encode(img->_data, &desc, img->_pitch, &n);
+        if (r) *len = (size_t)n;
+        return r;
+    }
+    // device pixels: encoded where they are, the stream comes back
+    const size_t bound = (size_t)gamut_hip_qoi_encode_bound(&desc);
+    hipStream_t st = thread_stream();
+    static thread_local PerDevice<DeviceScratch> out_pd;
+    uint8_t* d = nullptr;
+    try { d = (uint8_t*)out_pd.cur().get(bound, st); } catch (...) { d = nullptr; }
+    if (!d) return nullptr;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    if (gamut_hip_qoi_encode_batch_device(&src, &pitch, &desc, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
+    uint8_t* r = (uint8_t*)malloc((size_t)n);
+    if (!r) return nullptr;
+    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); free(r); return nullptr;
+    }
+    *len = (size_t)n;
+    return r;
+}
+int gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags)      // image.d:953-958
+{
+    if (!path) return 0;
+    size_t n = 0;
+    uint8_t* enc = gamut_image_save_to_memory(img, fif, flags, &n);
+    if (!enc) return 0;
+    FILE* f = fopen(path, "wb");
+    bool ok = f && fwrite(enc, 1, n, f) == n;
+    if (f && fclose(f) != 0) ok = false;
+    free(enc);
+    return ok;
+}
+void gamut_free_encoded_image(void* encoded) { free(encoded); }                          // image.d:32-36
+
 int   gamut_image_type(const gamut_image* img) { return img->_type; }
 int   gamut_image_width(const gamut_image* img) { return img->_width; }
 int   gamut_image_height(const gamut_image* img) { return img->_height; }

@@ -30,6 +30,8 @@ IMAGE_SIGNATURES = {
     "gamut_image_scanptr": (_vp, [_vp, _i]), "gamut_image_layerptr": (_vp, [_vp, _i, _i]), "gamut_image_disown_data": (_vp, [_vp]),
     "gamut_image_set_device_storage": (_i, [_vp, _i]), "gamut_image_is_device": (_i, [_vp]),
     "gamut_image_copy_pixels_to_host": (_i, [_vp, _i, _vp, C.c_int64]),
+    "gamut_image_save_to_memory": (_vp, [_vp, _i, _i, C.POINTER(_sz)]), "gamut_image_save_to_file": (_i, [_vp, _i, C.c_char_p, _i]),
+    "gamut_free_encoded_image": (None, [_vp]),
 }
 _bound = False
 
@@ -48,6 +50,7 @@ def lib():
 TO_GREYSCALE, TO_RGB, TO_ADD_ALPHA, TO_DROP_ALPHA, TO_PREMUL, TO_NO_PREMUL, TO_8BIT, TO_16BIT, TO_FP32 = range(9)
 LOAD_GREYSCALE, LOAD_ALPHA, LOAD_NO_ALPHA, LOAD_RGB = 0x10000, 0x20000, 0x40000, 0x80000
 LOAD_8BIT, LOAD_16BIT, LOAD_FP32, LOAD_PREMUL, LOAD_NO_PREMUL = 0x100000, 0x200000, 0x400000, 0x1000000, 0x2000000
+FORMAT_UNKNOWN, FORMAT_JPEG, FORMAT_PNG, FORMAT_QOI = -1, 0, 1, 2
 LAYOUT_DEFAULT, LAYOUT_VERT_FLIPPED, LAYOUT_VERT_STRAIGHT, LAYOUT_GAPLESS = 0, 512, 1024, 2048
 LAYOUT_MULTIPLICITY = {1: 0, 2: 1, 4: 2, 8: 3}
 LAYOUT_TRAILING = {0: 0, 1: 4, 3: 8, 7: 12}
@@ -154,6 +157,21 @@ class Image:
 
     def scanptr(self, y): return self.L.gamut_image_scanptr(self.h, y)
     def layerptr(self, layer, y): return self.L.gamut_image_layerptr(self.h, layer, y)
+
+    # saving (image.d:940-1011): QOI only, layer 0, encoded on the GPU
+    def save_to_memory(self, fif, flags=0):
+        """the encoded file as bytes, or None when the image cannot be saved in `fif`"""
+        n = _sz(0)
+        p = self.L.gamut_image_save_to_memory(self.h, fif, flags, C.byref(n))
+        if not p:
+            return None
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            self.L.gamut_free_encoded_image(p)
+    saveToMemory = save_to_memory
+
+    def saveToFile(self, fif, path, flags=0): return bool(self.L.gamut_image_save_to_file(self.h, fif, str(path).encode(), flags))
 
     @property
     def isDevice(self): return bool(self.L.gamut_image_is_device(self.h))

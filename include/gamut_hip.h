@@ -338,6 +338,21 @@ int   gamut_hip_qoi_decode_batch_device(const uint8_t* const* data, const int* s
 int   gamut_hip_qoi_decode_resident_device(const uint8_t* blob, int64_t blob_len, const int64_t* begin, const int* size,
                                            const gamut_hip_qoi_desc* descs, int count, int channels, const int64_t* out_offset,
                                            uint8_t* out, void* stream);
+/* QOI encode (qoi_encode, qoi.d:295-436), byte for byte.  The worst-case stream length (:313-315), or 0 when qoi_encode would refuse
+ * the desc (:303-311: zero width or height, channels other than 3 / 4, colorspace > 1, height >= 400000000 / width). */
+int64_t gamut_hip_qoi_encode_bound(const gamut_hip_qoi_desc* desc);
+/* drop-in for qoi_encode: the reference desc's pitchBytes passed beside it (rows of `data` are pitch_bytes apart, negative allowed);
+ * malloc'd stream of *out_len bytes, or NULL (bad arguments, no device: see last_error).  Encoded on the GPU. */
+void*   gamut_hip_qoi_encode(const void* data, const gamut_hip_qoi_desc* desc, int pitch_bytes, int* out_len);
+/* batch: image i is read from DEVICE memory at src[i] with rows src_pitch[i] apart (negative allowed, any alignment) and encoded to
+ * out + out_offset[i] (device), which must have gamut_hip_qoi_encode_bound(&descs[i]) bytes; nothing outside
+ * [out_offset[i], out_offset[i] + out_len[i]) is written.  out_len[i] / status_host[i] (host arrays; status_host may be NULL) receive
+ * the stream length and per-image status: an image the reference would refuse (or a NULL src[i], a negative out_offset[i]) gets
+ * GAMUT_HIP_ERR_INVALID_ARG and out_len 0, the others are still encoded, and the call returns the status of the lowest-numbered
+ * refused image.  Returns when the encode has finished. */
+int     gamut_hip_qoi_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_qoi_desc* descs,
+                                          int count, const int64_t* out_offset, uint8_t* out, int64_t* out_len,
+                                          int* status_host, void* stream);
 
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
