@@ -137,6 +137,15 @@ extern(C)
     int   gamut_hip_qoi_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(gamut_hip_qoi_desc)* descs,
                                             int count, const(long)* out_offset, ubyte* out_, long* out_len,
                                             int* status_host, void* stream);
+    long  gamut_hip_jpeg_encode_bound(int width, int height, int comp, int quality);
+    void* gamut_hip_jpeg_encode(const(void)* data, int width, int height, int comp, int pitch, int quality, int* out_len);
+    // stbi_write_func (stb_image_write.d) with C linkage
+    alias gamut_hip_jpeg_write_func = void function(void* context, const(void)* data, int size);
+    int   gamut_hip_jpeg_write_to_func(gamut_hip_jpeg_write_func func, void* context, int x, int y, int comp, const(void)* data,
+                                       int pitch, int quality);
+    int   gamut_hip_jpeg_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(int)* width, const(int)* height,
+                                             const(int)* comp, const(int)* quality, int count, const(long)* out_offset, ubyte* out_,
+                                             long* out_len, int* status_host, void* stream);
 
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }
@@ -172,13 +181,13 @@ extern(C)
 }
 
 // ================================================================================================================
-// The callbacks.  Way (2): four trampolines with C linkage that forward to the reference's extern(D) functions.
-// They live next to their targets: the JPEG one in plugins/jpeg.d, the three stb ones in codecs/stbdec.d.
+// The callbacks.  Way (2): five trampolines with C linkage that forward to the reference's extern(D) functions.
+// They live next to their targets: the two JPEG ones in plugins/jpeg.d, the three stb ones in codecs/stbdec.d.
 // ================================================================================================================
 
 version (GamutHipTrampolines)
 {
-    import gamut.plugins.jpeg : stream_read_jpeg;          // plugins/jpeg.d:167, extern(D)
+    import gamut.plugins.jpeg : stream_read_jpeg, stb_stream_write;   // plugins/jpeg.d:167, :180, extern(D)
     import gamut.codecs.stbdec : stb_read, stb_skip, stb_eof, IOAndHandle;   // codecs/stbdec.d:143-165, extern(D)
 
     extern(C) int gamut_hip_tramp_read_jpeg(void* pBuf, int max_bytes_to_read, bool* pEOF_flag, void* userData) @system
@@ -188,6 +197,7 @@ version (GamutHipTrampolines)
     extern(C) int  gamut_hip_tramp_stb_read(void* user, char* data, int size) @system { return stb_read(user, data, size); }
     extern(C) void gamut_hip_tramp_stb_skip(void* user, int n) @system               { stb_skip(user, n); }
     extern(C) int  gamut_hip_tramp_stb_eof(void* user) @system                        { return stb_eof(user); }
+    extern(C) void gamut_hip_tramp_stb_write(void* context, const(void)* data, int size) @system { stb_stream_write(context, data, size); }
 
     /// what `initSTBCallbacks` (stbdec.d:126-133) becomes for the HIP path
     void initHipSTBCallbacks(IOStream* io, IOHandle handle, IOAndHandle* ioh, gamut_hip_stbi_io_callbacks* cb) @system
@@ -207,4 +217,7 @@ version (GamutHipTrampolines)
     //     gamut_hip_stbi_io_callbacks cb;  initHipSTBCallbacks(io, handle, &ioh, &cb);
     //     bool is16bit = gamut_hip_stbi_png_is16_from_callbacks(&cb, &ioh) != 0;
     //     ... decoded = gamut_hip_stbi_load_from_callbacks(&cb, &ioh, &width, &height, &components, requestedComp, &ppmX, &ppmY, &pixelRatio);
+    // saveJPEG, plugins/jpeg.d:141 -- `stbi_write_jpg_to_func(&stb_stream_write, userPointer, ...)` becomes
+    //     int res = gamut_hip_jpeg_write_to_func(&gamut_hip_tramp_stb_write, userPointer, image._width, image._height, components,
+    //                                            image._data, image._pitch, quality);
 }

@@ -89,6 +89,11 @@ SIGNATURES = {
     "gamut_hip_qoi_encode": (_vp, [_vp, C.POINTER(QoiDesc), _i, _pi]),
     "gamut_hip_qoi_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(QoiDesc), _i, C.POINTER(_i64), _vp, C.POINTER(_i64),
                                            C.POINTER(_i), _vp]),
+    "gamut_hip_jpeg_encode_bound": (_i64, [_i, _i, _i, _i]),
+    "gamut_hip_jpeg_encode": (_vp, [_vp, _i, _i, _i, _i, _i, _pi]),
+    "gamut_hip_jpeg_write_to_func": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
+    "gamut_hip_jpeg_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), _pi, _pi, _pi, _pi, _i, C.POINTER(_i64), _vp,
+                                            C.POINTER(_i64), _pi, _vp]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),
@@ -126,6 +131,7 @@ SIGNATURES = {
 }
 
 JPEG_STREAM_READ_FUNC = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_ubyte), C.c_void_p)      # jpegload.d:70
+JPEG_WRITE_FUNC = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)                                     # stb_image_write.d stbi_write_func
 
 
 class StbiIoCallbacks(C.Structure):                                                                       # stbdec.d:408-419

@@ -598,12 +598,10 @@ int gamut_image_copy_pixels_to_host(gamut_image* img, int layer, void* dst, int6
     return 1;
 }
 
-// ---- saving (image.d:940-1011): saveToStream -> g_plugins[fif].saveProc; only saveQOI (plugins/qoi.d:149-184) has an encoder here ----
-uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980
+// ---- saving (image.d:940-1011): saveToStream -> g_plugins[fif].saveProc; saveQOI (plugins/qoi.d:149-184) and saveJPEG
+// (plugins/jpeg.d:112-148) have encoders here ----
+static uint8_t* save_qoi(gamut_image* img, size_t* len)
 {
-    (void)flags;                                               // saveQOI ignores them
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data || fif != GAMUT_FORMAT_QOI) return nullptr;
     gamut_hip_qoi_desc desc{};
     desc.width = (uint32_t)img->_width; desc.height = (uint32_t)img->_height; desc.colorspace = 0;       // QOI_SRGB
     if (img->_type == GAMUT_PIXEL_rgb8) desc.channels = 3;
@@ -632,6 +630,56 @@ uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t
     }
     *len = (size_t)n;
     return r;
+}
+
+// saveJPEG: l8 -> 1 component, rgb8 -> 3, everything else (rgba8 included: stb would drop the alpha) refused; quality 90 (4:2:0)
+static uint8_t* save_jpeg(gamut_image* img, size_t* len)
+{
+    int comp;
+    if (img->_type == GAMUT_PIXEL_l8) comp = 1;
+    else if (img->_type == GAMUT_PIXEL_rgb8) comp = 3;
+    else return nullptr;
+    const int quality = 90, w = img->_width, h = img->_height;
+    if (gamut_hip_jpeg_encode_bound(w, h, comp, quality) == 0) return nullptr;
+    if (!img->_device) {                                       // host pixels: the stbi_write_jpg_to_func drop-in, as saveJPEG calls it
+        struct Sink { std::vector<uint8_t> b; } sink;
+        auto put = [](void* ctx, const void* data, int size) {
+            Sink* s = (Sink*)ctx;
+            try { s->b.insert(s->b.end(), (const uint8_t*)data, (const uint8_t*)data + size); } catch (...) { s->b.clear(); }
+        };
+        if (!gamut_hip_jpeg_write_to_func(put, &sink, w, h, comp, img->_data, (int)img->_pitch, quality) || sink.b.empty()) return nullptr;
+        uint8_t* r = (uint8_t*)malloc(sink.b.size());
+        if (!r) return nullptr;
+        memcpy(r, sink.b.data(), sink.b.size());
+        *len = sink.b.size();
+        return r;
+    }
+    const size_t bound = (size_t)gamut_hip_jpeg_encode_bound(w, h, comp, quality);
+    hipStream_t st = thread_stream();
+    static thread_local PerDevice<DeviceScratch> out_pd;
+    uint8_t* d = nullptr;
+    try { d = (uint8_t*)out_pd.cur().get(bound, st); } catch (...) { d = nullptr; }
+    if (!d) return nullptr;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    const int32_t W = w, H = h, Cc = comp, Q = quality;
+    if (gamut_hip_jpeg_encode_batch_device(&src, &pitch, &W, &H, &Cc, &Q, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
+    uint8_t* r = (uint8_t*)malloc((size_t)n);
+    if (!r) return nullptr;
+    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); free(r); return nullptr;
+    }
+    *len = (size_t)n;
+    return r;
+}
+
+uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980
+{
+    (void)flags;                                               // saveQOI and saveJPEG ignore them
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
+    if (fif == GAMUT_FORMAT_QOI) return save_qoi(img, len);
+    if (fif == GAMUT_FORMAT_JPEG) return save_jpeg(img, len);
+    return nullptr;
 }
 int gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags)      // image.d:953-958
 {

@@ -158,7 +158,7 @@ class Image:
     def scanptr(self, y): return self.L.gamut_image_scanptr(self.h, y)
     def layerptr(self, layer, y): return self.L.gamut_image_layerptr(self.h, layer, y)
 
-    # saving (image.d:940-1011): QOI only, layer 0, encoded on the GPU
+    # saving (image.d:940-1011): QOI and JPEG, layer 0, encoded on the GPU
     def save_to_memory(self, fif, flags=0):
         """the encoded file as bytes, or None when the image cannot be saved in `fif`"""
         n = _sz(0)

@@ -354,6 +354,32 @@ int     gamut_hip_qoi_encode_batch_device(const uint8_t* const* src, const int64
                                           int count, const int64_t* out_offset, uint8_t* out, int64_t* out_len,
                                           int* status_host, void* stream);
 
+/* JPEG encode (stbi_write_jpg_core, stb_image_write.d:632-880), byte for byte: baseline, three components (comp 1 and 2 are grey,
+ * the alpha of comp 2 and 4 is ignored), 4:2:0 when quality <= 90 (0 means 90) and 4:4:4 above, standard Annex K tables.
+ * Refused: NULL data, width or height below 1, comp outside 1..4, and -- unlike the reference, which writes a truncated SOF0 --
+ * width or height above 65535.
+ * The worst-case stream length, or 0 when refused: 607 + 2 * ceil((blocks * 1660 + 7) / 8) + 2 bytes (1660 bits per 8x8 block at
+ * most, every data byte possibly stuffed). */
+int64_t gamut_hip_jpeg_encode_bound(int width, int height, int comp, int quality);
+/* host pixels (rows `pitch` bytes apart, negative allowed) -> malloc'd stream of *out_len bytes, or NULL (see last_error).  Encoded
+ * on the GPU through pinned staging. */
+void*   gamut_hip_jpeg_encode(const void* data, int width, int height, int comp, int pitch, int quality, int* out_len);
+/* drop-in for stbi_write_jpg_to_func: returns 1, or 0 on refusal without calling func.  The bytes handed to func, concatenated,
+ * are the reference's; they come in one call rather than the reference's many small ones. */
+typedef void (*gamut_hip_jpeg_write_func)(void* context, const void* data, int size);
+int     gamut_hip_jpeg_write_to_func(gamut_hip_jpeg_write_func func, void* context, int x, int y, int comp, const void* data, int pitch,
+                                     int quality);
+/* batch: image i is read from DEVICE memory at src[i] (rows src_pitch[i] apart, negative allowed, any alignment), width[i] x
+ * height[i], comp[i], quality[i] (quality may be NULL: 90 for every image), and encoded to out + out_offset[i] (device), which
+ * must have gamut_hip_jpeg_encode_bound(...) bytes; nothing outside [out_offset[i], out_offset[i] + out_len[i]) is written.
+ * out_len[i] / status_host[i] (host arrays; status_host may be NULL) receive the stream length and per-image status: a refused
+ * image (or a NULL src[i], a negative out_offset[i]) gets GAMUT_HIP_ERR_INVALID_ARG and out_len 0, the others are still encoded,
+ * and the call returns the status of the lowest-numbered refused image.  Returns when the encode has finished. */
+int     gamut_hip_jpeg_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const int32_t* width,
+                                           const int32_t* height, const int32_t* comp, const int32_t* quality, int count,
+                                           const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host,
+                                           void* stream);
+
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
  * procedures, a signature test each: plugins/jpeg.d:106-110, png.d:165-169, qoi.d:143-147) picks g_plugins[fif].loadProc

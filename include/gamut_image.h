@@ -9,7 +9,7 @@
  * LoadFlags / LayoutConstraints bits (types.d:139-348).  Pixel storage is host malloc memory exactly as
  * in the reference (the user may disown and free() it); every pixel operation (decode, convertTo) runs
  * on the GPU through gamut_hip_* -- there is no CPU pixel path.
- * Formats: JPEG (baseline), PNG and QOI are read; QOI is written (saveToMemory / saveToFile); other signatures report
+ * Formats: JPEG (baseline), PNG and QOI are read; QOI and JPEG are written (saveToMemory / saveToFile); other signatures report
  * "Unidentified image format".
  */
 #ifndef GAMUT_IMAGE_H
@@ -119,11 +119,12 @@ int gamut_image_is_device(const gamut_image* img);
 /* one layer, logical top-down order, into host rows of dst_pitch bytes -- for host and device images alike */
 int gamut_image_copy_pixels_to_host(gamut_image* img, int layer, void* dst, int64_t dst_pitch);
 
-/* ---- saving (image.d:940-1011, saveQOI plugins/qoi.d:149-184) ---------------------------------------------------------
- * Layer 0 in logical top-down order, encoded on the GPU (gamut_hip_qoi_encode*): device-resident images straight from HBM, host
- * images through pinned staging.  QOI only: JPEG and PNG have no encoder here and are refused, as is an errored image, an unknown
- * format or a type other than rgb8 / rgba8.  The colorspace written is sRGB; flags are ignored (as saveQOI does).  The image's
- * state and error are left as they were. */
+/* ---- saving (image.d:940-1011, saveQOI plugins/qoi.d:149-184, saveJPEG plugins/jpeg.d:112-148) ------------------------------
+ * Layer 0 in logical top-down order, encoded on the GPU: device-resident images straight from HBM, host images through pinned
+ * staging.  QOI (gamut_hip_qoi_encode*): rgb8 / rgba8, colorspace sRGB.  JPEG (gamut_hip_jpeg_encode*, byte for byte what
+ * stbi_write_jpg_to_func writes): l8 (one component) / rgb8 (three), quality 90, so 4:2:0; rgba8 and every other type are refused
+ * as saveJPEG refuses them.  PNG has no encoder here and is refused, as is an errored image or an unknown format.  Flags are
+ * ignored (as both plugins do).  The image's state and error are left as they were. */
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len);   /* image.d:966-980; NULL (and *len = 0) on refusal */
 int      gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags); /* image.d:953-958; 1 on success */
 void     gamut_free_encoded_image(void* encoded);                                       /* image.d:32-36 */
