@@ -146,6 +146,14 @@ extern(C)
     int   gamut_hip_jpeg_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(int)* width, const(int)* height,
                                              const(int)* comp, const(int)* quality, int count, const(long)* out_offset, ubyte* out_,
                                              long* out_len, int* status_host, void* stream);
+    // PNG encode: the reference's container and filter stream around a GPU-built zlib stream
+    long  gamut_hip_png_encode_bound(int width, int height, int comp, int is16bit);
+    void* gamut_hip_png_write_to_mem(const(void)* pixels, int stride_bytes, int x, int y, int n, int* out_len, int is16bit,
+                                     int force_filter, int compression_level);
+    int   gamut_hip_png_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(int)* width, const(int)* height,
+                                            const(int)* comp, const(int)* is16bit, const(int)* force_filter, const(int)* level,
+                                            int count, const(long)* out_offset, ubyte* out_, long* out_len, int* status_host,
+                                            void* stream);
 
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }
@@ -220,4 +228,7 @@ version (GamutHipTrampolines)
     // saveJPEG, plugins/jpeg.d:141 -- `stbi_write_jpg_to_func(&stb_stream_write, userPointer, ...)` becomes
     //     int res = gamut_hip_jpeg_write_to_func(&gamut_hip_tramp_stb_write, userPointer, image._width, image._height, components,
     //                                            image._data, image._pitch, quality);
+    // savePNG, plugins/png.d:208 -- `stbi_write_png_to_mem(pixels, pitch, width, height, channels, &len, is16Bit, ...)` becomes
+    //     ubyte* encoded = cast(ubyte*) gamut_hip_png_write_to_mem(pixels, pitch, width, height, channels, &len, is16Bit,
+    //                                                              force_filter, compression_level);
 }

@@ -94,6 +94,10 @@ SIGNATURES = {
     "gamut_hip_jpeg_write_to_func": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i]),
     "gamut_hip_jpeg_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), _pi, _pi, _pi, _pi, _i, C.POINTER(_i64), _vp,
                                             C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_png_encode_bound": (_i64, [_i, _i, _i, _i]),
+    "gamut_hip_png_write_to_mem": (_vp, [_vp, _i, _i, _i, _i, _pi, _i, _i, _i]),
+    "gamut_hip_png_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), _pi, _pi, _pi, _pi, _pi, _pi, _i, C.POINTER(_i64), _vp,
+                                           C.POINTER(_i64), _pi, _vp]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

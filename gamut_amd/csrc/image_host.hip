@@ -599,7 +599,7 @@ int gamut_image_copy_pixels_to_host(gamut_image* img, int layer, void* dst, int6
 }
 
 // ---- saving (image.d:940-1011): saveToStream -> g_plugins[fif].saveProc; saveQOI (plugins/qoi.d:149-184) and saveJPEG
-// (plugins/jpeg.d:112-148) have encoders here ----
+// (plugins/jpeg.d:112-148) have encoders here; savePNG (plugins/png.d:172-221) has entries of its own further down ----
 static uint8_t* save_qoi(gamut_image* img, size_t* len)
 {
     gamut_hip_qoi_desc desc{};
@@ -670,6 +670,70 @@ static uint8_t* save_jpeg(gamut_image* img, size_t* len)
     }
     *len = (size_t)n;
     return r;
+}
+
+// savePNG (plugins/png.d:172-221): the eight integer types, flags read (:201-206), pitch passed through as stb's signed stride
+static uint8_t* save_png(gamut_image* img, int flags, size_t* len)
+{
+    int comp, is16 = 0;
+    switch (img->_type) {
+        case GAMUT_PIXEL_l8: comp = 1; break;
+        case GAMUT_PIXEL_la8: comp = 2; break;
+        case GAMUT_PIXEL_rgb8: comp = 3; break;
+        case GAMUT_PIXEL_rgba8: comp = 4; break;
+        case GAMUT_PIXEL_l16: comp = 1; is16 = 1; break;
+        case GAMUT_PIXEL_la16: comp = 2; is16 = 1; break;
+        case GAMUT_PIXEL_rgb16: comp = 3; is16 = 1; break;
+        case GAMUT_PIXEL_rgba16: comp = 4; is16 = 1; break;
+        default: return nullptr;
+    }
+    const int force_filter = (flags & GAMUT_ENCODE_PNG_FILTER_FAST) ? 0 : -1;
+    int level = flags & 15;
+    if (level == GAMUT_ENCODE_PNG_COMPRESSION_DEFAULT) level = GAMUT_ENCODE_PNG_COMPRESSION_5;
+    level--;
+    const int w = img->_width, h = img->_height;
+    if (level < 0 || level > 10 || gamut_hip_png_encode_bound(w, h, comp, is16) == 0) return nullptr;
+    if (!img->_device) {                                       // host pixels: the stbi_write_png_to_mem drop-in, as savePNG calls it
+        int n = 0;
+        uint8_t* r = (uint8_t*)gamut_hip_png_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, &n, is16, force_filter, level);
+        if (r) *len = (size_t)n;
+        return r;
+    }
+    const size_t bound = (size_t)gamut_hip_png_encode_bound(w, h, comp, is16);
+    hipStream_t st = thread_stream();
+    static thread_local PerDevice<DeviceScratch> out_pd;
+    uint8_t* d = nullptr;
+    try { d = (uint8_t*)out_pd.cur().get(bound, st); } catch (...) { d = nullptr; }
+    if (!d) return nullptr;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    const int32_t W = w, H = h, Cc = comp, S = is16, F = force_filter, Lv = level;
+    if (gamut_hip_png_encode_batch_device(&src, &pitch, &W, &H, &Cc, &S, &F, &Lv, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
+    uint8_t* r = (uint8_t*)malloc((size_t)n);
+    if (!r) return nullptr;
+    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); free(r); return nullptr;
+    }
+    *len = (size_t)n;
+    return r;
+}
+
+uint8_t* gamut_image_save_png_to_memory(gamut_image* img, int flags, size_t* len)
+{
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
+    return save_png(img, flags, len);
+}
+int gamut_image_save_png_to_file(gamut_image* img, const char* path, int flags)
+{
+    if (!path) return 0;
+    size_t n = 0;
+    uint8_t* enc = gamut_image_save_png_to_memory(img, flags, &n);
+    if (!enc) return 0;
+    FILE* f = fopen(path, "wb");
+    bool ok = f && fwrite(enc, 1, n, f) == n;
+    if (f && fclose(f) != 0) ok = false;
+    free(enc);
+    return ok;
 }
 
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980

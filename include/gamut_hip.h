@@ -380,6 +380,34 @@ int     gamut_hip_jpeg_encode_batch_device(const uint8_t* const* src, const int6
                                            const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host,
                                            void* stream);
 
+/* PNG encode (stbi_write_png_to_mem, stb_image_write.d:254-451).  Container and filter stream are the reference's byte for byte:
+ * inflate(IDAT payload) is the `filt` buffer it hands to its compressor (per-row filter choice included) and every byte outside
+ * the IDAT payload is what it writes around a payload of that length.  The DEFLATE stream is this library's own (the reference's
+ * miniz stream is not reproduced): a valid, deterministic zlib stream built on the GPU from independent blocks of 8192 filtered
+ * bytes, each the smallest of stored / fixed / dynamic Huffman, matches of 3..258 at the distances filtered PNG data repeats at.
+ * comp 1..4 (l, la, rgb, rgba), is16bit: samples are native 16-bit and written big-endian.  force_filter 0..4 forces a filter,
+ * anything else selects per row as the reference does.  compression_level 0 writes stored blocks only; 1..10 all stand for the one
+ * effort of the GPU compressor; no level produces a larger file than level 0.
+ * Refused: NULL pixels, width or height below 1, comp outside 1..4, level outside 0..10, and any image whose filtered stream
+ * (width * comp * (is16bit ? 2 : 1) + 1) * height does not fit a positive int (the reference's int arithmetic would wrap).
+ * The worst-case file length, or 0 when refused, with L the filtered length above: 57 + 6 + L + 5 * ceil(L / 8192) -- the container,
+ * the zlib header and Adler-32, and L bytes in stored blocks of 8192. */
+int64_t gamut_hip_png_encode_bound(int width, int height, int comp, int is16bit);
+/* drop-in for stbi_write_png_to_mem (same argument list): host pixels (rows stride_bytes apart, negative allowed) through pinned
+ * staging -> malloc'd file of *out_len bytes, or NULL on refusal (see last_error). */
+void*   gamut_hip_png_write_to_mem(const void* pixels, int stride_bytes, int x, int y, int n, int* out_len, int is16bit,
+                                   int force_filter, int compression_level);
+/* batch: image i is read from DEVICE memory at src[i] (rows src_pitch[i] apart, negative allowed, any alignment) and encoded to
+ * out + out_offset[i] (device), which must have gamut_hip_png_encode_bound(...) bytes; nothing outside
+ * [out_offset[i], out_offset[i] + out_len[i]) is written.  force_filter may be NULL (-1: select for every image), level may be
+ * NULL (5).  out_len[i] / status_host[i] (host arrays; status_host may be NULL) receive the file length and per-image status: a
+ * refused image (or a NULL src[i], a negative out_offset[i]) gets GAMUT_HIP_ERR_INVALID_ARG and out_len 0, the others are still
+ * encoded, and the call returns the status of the lowest-numbered refused image.  Returns when the encode has finished. */
+int     gamut_hip_png_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const int32_t* width,
+                                          const int32_t* height, const int32_t* comp, const int32_t* is16bit,
+                                          const int32_t* force_filter, const int32_t* level, int count, const int64_t* out_offset,
+                                          uint8_t* out, int64_t* out_len, int* status_host, void* stream);
+
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
  * procedures, a signature test each: plugins/jpeg.d:106-110, png.d:165-169, qoi.d:143-147) picks g_plugins[fif].loadProc

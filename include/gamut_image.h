@@ -9,7 +9,7 @@
  * LoadFlags / LayoutConstraints bits (types.d:139-348).  Pixel storage is host malloc memory exactly as
  * in the reference (the user may disown and free() it); every pixel operation (decode, convertTo) runs
  * on the GPU through gamut_hip_* -- there is no CPU pixel path.
- * Formats: JPEG (baseline), PNG and QOI are read; QOI and JPEG are written (saveToMemory / saveToFile); other signatures report
+ * Formats: JPEG (baseline), PNG and QOI are read; QOI and JPEG are written (saveToMemory / saveToFile), PNG through savePNG's own entries; other signatures report
  * "Unidentified image format".
  */
 #ifndef GAMUT_IMAGE_H
@@ -123,11 +123,25 @@ int gamut_image_copy_pixels_to_host(gamut_image* img, int layer, void* dst, int6
  * Layer 0 in logical top-down order, encoded on the GPU: device-resident images straight from HBM, host images through pinned
  * staging.  QOI (gamut_hip_qoi_encode*): rgb8 / rgba8, colorspace sRGB.  JPEG (gamut_hip_jpeg_encode*, byte for byte what
  * stbi_write_jpg_to_func writes): l8 (one component) / rgb8 (three), quality 90, so 4:2:0; rgba8 and every other type are refused
- * as saveJPEG refuses them.  PNG has no encoder here and is refused, as is an errored image or an unknown format.  Flags are
- * ignored (as both plugins do).  The image's state and error are left as they were. */
+ * as saveJPEG refuses them.  GAMUT_FORMAT_PNG is not dispatched from these two generic entries yet (they return NULL / 0 for it, as
+ * for an errored image or an unknown format): PNG is saved through gamut_image_save_png_to_memory / _to_file below.  Flags are
+ * ignored here (as both plugins do).  The image's state and error are left as they were. */
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len);   /* image.d:966-980; NULL (and *len = 0) on refusal */
 int      gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags); /* image.d:953-958; 1 on success */
 void     gamut_free_encoded_image(void* encoded);                                       /* image.d:32-36 */
+/* savePNG (plugins/png.d:172-221; gamut_hip_png_*): l8 / la8 / rgb8 / rgba8 / l16 / la16 / rgb16 / rgba16, every other type refused.
+ * Unlike the other two plugins this one reads its flags (:201-206, types.d:220-248): level = flags & 15, 0 meaning
+ * ENCODE_PNG_COMPRESSION_5, minus 1 (so 12..15 are refused); GAMUT_ENCODE_PNG_FILTER_FAST forces filter 0. */
+enum {
+    GAMUT_ENCODE_PNG_COMPRESSION_DEFAULT = 0, GAMUT_ENCODE_PNG_COMPRESSION_FAST = 2, GAMUT_ENCODE_PNG_COMPRESSION_SMALL = 10,
+    GAMUT_ENCODE_PNG_COMPRESSION_0 = 1, GAMUT_ENCODE_PNG_COMPRESSION_1 = 2, GAMUT_ENCODE_PNG_COMPRESSION_2 = 3,
+    GAMUT_ENCODE_PNG_COMPRESSION_3 = 4, GAMUT_ENCODE_PNG_COMPRESSION_4 = 5, GAMUT_ENCODE_PNG_COMPRESSION_5 = 6,
+    GAMUT_ENCODE_PNG_COMPRESSION_6 = 7, GAMUT_ENCODE_PNG_COMPRESSION_7 = 8, GAMUT_ENCODE_PNG_COMPRESSION_8 = 9,
+    GAMUT_ENCODE_PNG_COMPRESSION_9 = 10, GAMUT_ENCODE_PNG_COMPRESSION_10 = 11,
+    GAMUT_ENCODE_PNG_FILTER_DEFAULT = 0, GAMUT_ENCODE_PNG_FILTER_SMALL = 0, GAMUT_ENCODE_PNG_FILTER_FAST = 16
+};
+uint8_t* gamut_image_save_png_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
+int      gamut_image_save_png_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
 
 #ifdef __cplusplus
 }

@@ -220,6 +220,34 @@ def batch_cases():
     return n
 
 
+def png_encode_cases():
+    """gamut_hip_png_encode_batch_device: every source ends with its allocation (positive and negative pitch), the output holds the
+    bounds and not one byte more"""
+    rng = np.random.default_rng(6)
+    n = 0
+    for shapes in ([(33, 9, 3, 0), (130, 70, 4, 0), (5, 1, 1, 1)], [(8191, 1, 1, 0), (64, 300, 2, 1), (1, 1, 4, 1)], [(700, 64, 4, 0)]):
+        for level in (5, 0):
+            k = len(shapes)
+            src = (C.c_void_p * k)(); pitch = (C.c_int64 * k)(); W = (C.c_int * k)(); H = (C.c_int * k)(); CO = (C.c_int * k)()
+            S = (C.c_int * k)(); F = (C.c_int * k)(); LV = (C.c_int * k)(); offs = (C.c_int64 * k)(); lens = (C.c_int64 * k)(); st = (C.c_int * k)()
+            total = 0
+            for i, (w, h, c, s16) in enumerate(shapes):
+                rb = w * c * (2 if s16 else 1)
+                px = (rng.integers(0, 256, (h, rb), dtype=np.uint8) // 32 * 32)
+                d = up_end(px)
+                neg = i % 2 == 1
+                src[i] = d + (h - 1) * rb if neg else d
+                pitch[i] = -rb if neg else rb
+                W[i], H[i], CO[i], S[i], F[i], LV[i] = w, h, c, s16, (i + n) % 6 - 1, level
+                offs[i] = total
+                total += L.gamut_hip_png_encode_bound(w, h, c, s16)
+            dout = at_end(total)
+            _capi.check(L.gamut_hip_png_encode_batch_device(src, pitch, W, H, CO, S, F, LV, k, offs, dout, lens, st, None))
+            assert all(lens[i] > 57 for i in range(k))
+            free_all(); n += 1
+    return n
+
+
 if len(sys.argv) > 1 and sys.argv[1] == "control":
     print("control: converting one row more than the buffers hold -- a memory access fault is the expected outcome", flush=True)
     L.gamut_hip_device_free(L.gamut_hip_device_malloc(64 << 20))
@@ -238,5 +266,6 @@ print("jpeg", jpeg_cases(), "cases ok", flush=True)
 print("convert", convert_cases(), "cases ok", flush=True)
 print("batch / qoi / entropy", batch_cases(), "cases ok", flush=True)
 print("inflate", inflate_cases(), "cases ok", flush=True)
+print("png encode", png_encode_cases(), "cases ok", flush=True)
 print("random geometries", random_cases(), "cases ok", flush=True)
 print("oob_probe: no access outside any buffer")
