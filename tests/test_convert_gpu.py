@@ -252,3 +252,149 @@ def test_more_gapless_layers_than_one_launch_indexes(hip, w, h):
     finally:
         for p in (src, mid, back):
             L.gamut_hip_device_free(p)
+
+
+# ---------------------------------------------------------------- row geometry: wide rows with a pitch of their own
+# The guard on both sides of every buffer below is wider than the longest run one wave stores in one go (64 units of 24 bytes,
+# convert.hip's staged store): a run that starts or ends in the wrong place lands inside the allocation, where the comparison
+# of the whole buffer sees it.
+GUARD = 4096
+
+
+def _up16(n):
+    return (n + 15) // 16 * 16
+
+
+def _unit_pixels(s, d):
+    """pixels per thread for a pair of pixel sizes, as convert.hip chooses them: the wider side whole dwords and >= 16 bytes"""
+    wide = max(s, d)
+    g = 4 // np.gcd(wide, 4)
+    while g * wide < 16:
+        g *= 2
+    return int(g)
+
+
+def _vec_bytes(unit_bytes):
+    return next(v for v in (16, 8, 4, 2, 1) if unit_bytes % v == 0)
+
+
+def _convert_geometry(hip, rng, src, dst, w, h, spitch, dpitch, sflip=False, dflip=False, layers=1, sgap=0, dgap=0, slead=0, dlead=0):
+    """`layers` layers of h rows, |pitch| bytes apart (bottom-up when flipped), `gap` bytes between layers, `lead` bytes in front
+    to move the base address, GUARD bytes around it all; everything in the source that is not a pixel is random.  The oracle converts layer by layer into a 0xA5-filled buffer; the
+    device converts all layers in one call into another; the two buffers are compared whole.  -> None, or a description of the difference"""
+    st, dt = PT[src], PT[dst]
+    assert spitch >= w * PT_SIZE[st] and dpitch >= w * PT_SIZE[dt]
+    sl, dl = spitch * h + sgap, dpitch * h + dgap
+    sbuf = rng.integers(0, 256, GUARD + slead + sl * layers + GUARD, dtype=np.uint8)       # pads, gaps and guards of the source are noise:
+    #                                                                                        a copy that takes too much of a row shows
+    exp = np.full(GUARD + dlead + dl * layers + GUARD, 0xA5, np.uint8)
+    inter = O.lib().orc_scanlines_inter_type(st, dt)
+    ibuf = np.zeros(w * 16 + 16, np.uint8)
+    for l in range(layers):
+        px = gen.make_pixels(src, w * h, rng)
+        packed, soff, sp = gen.pack_rows(px, w, h, spitch, flipped=sflip)
+        at = GUARD + slead + l * sl
+        for y in range(h):
+            sbuf[at + y * spitch:at + y * spitch + w * PT_SIZE[st]] = packed[y * spitch:y * spitch + w * PT_SIZE[st]]
+        doff, dp = ((h - 1) * dpitch, -dpitch) if dflip else (0, dpitch)
+        assert O.lib().orc_scanlines_convert(st, sbuf.ctypes.data + at + soff, sp, dt, exp.ctypes.data + GUARD + dlead + l * dl + doff, dp,
+                                             w, h, inter, ibuf.ctypes.data)
+    got = _run_device(hip, st, dt, sbuf, GUARD + slead + soff, sp, exp.size, GUARD + dlead + doff, dp, w, h, layers, sl, dl)
+    if np.array_equal(got, exp):
+        return None
+    bad = np.flatnonzero(got != exp)
+    where = []
+    for b in bad[:4]:
+        rel = int(b) - GUARD - dlead
+        l, in_layer = divmod(rel, dl) if 0 <= rel < dl * layers else (-1, rel)
+        where.append(f"byte {int(b)} (layer {l}, stored row {in_layer // dpitch}, column byte {in_layer % dpitch}): got {got[b]} exp {exp[b]}")
+    return (f"{src}->{dst} w={w} h={h} layers={layers} spitch={-spitch if sflip else spitch} dpitch={-dpitch if dflip else dpitch} "
+            f"gaps=({sgap},{dgap}) leads=({slead},{dlead}): {bad.size} bytes differ; " + "; ".join(where))
+
+
+@pytest.mark.parametrize("src", PIXEL_TYPES)
+def test_all_pairs_wide_padded_rows(hip, src):
+    """every destination type from `src` at widths of more than one wave of units per row (1100 pixels; the largest unit is 16
+    pixels) and with a partial unit at the end of every row (2053 is prime), 5 rows with a pitch of their own: rows start in the
+    middle of a wave, so one launch holds waves wholly inside a row (staged for rgb8 / rgb16 / rgbf32 destinations), waves that
+    cross a row end, and row tails.  Padded 16-aligned pitches (the vector kernel), the same bottom-up, the destination pitch 3
+    bytes off (the byte kernel), and a gapless source into a padded destination."""
+    rng = np.random.default_rng(4321 + PT[src])
+    failures = []
+    for dst in PIXEL_TYPES:
+        for w in (1100, 2053):
+            srow, drow = w * PT_SIZE[PT[src]], w * PT_SIZE[PT[dst]]
+            sp, dp = _up16(srow) + 16, _up16(drow) + 16
+            for kw in (dict(spitch=sp, dpitch=dp), dict(spitch=sp, dpitch=dp, sflip=True, dflip=True), dict(spitch=sp, dpitch=dp + 3),
+                       dict(spitch=srow, dpitch=dp)):
+                bad = _convert_geometry(hip, rng, src, dst, w, 5, **kw)
+                if bad:
+                    failures.append(bad)
+    assert not failures, f"{len(failures)} layouts differ:\n" + "\n".join(failures[:6])
+
+
+@pytest.mark.parametrize("dst", ["rgb8", "rgb16", "rgbf32"])
+def test_staged_store_unaligned_run(hip, dst):
+    """the staged store writes 16 bytes per lane from the wave's first address: with the destination base at every multiple of the
+    pair's vector size below 16 the vector kernel still runs, and those 16-byte stores land on addresses that are no multiple of
+    16.  A base 1 byte off takes the byte kernel (for every pair whose unit is not made of single bytes)."""
+    rng = np.random.default_rng(555 + PT[dst])
+    failures = []
+    for src in ("l8", "rgba8", "rgbaf32", "rgb16"):
+        ss, ds = PT_SIZE[PT[src]], PT_SIZE[PT[dst]]
+        vec = _vec_bytes(_unit_pixels(ss, ds) * ds)
+        for w in (1100, 4096 + 7):
+            for dlead in sorted(set(range(0, 16, vec)) | {1}):
+                bad = _convert_geometry(hip, rng, src, dst, w, 3, _up16(w * ss) + 16, _up16(w * ds) + 16, dlead=dlead)
+                if bad:
+                    failures.append(bad)
+                bad = _convert_geometry(hip, rng, src, dst, w, 3, _up16(w * ss) + 16, _up16(w * ds) + 16, dlead=dlead, dflip=True)
+                if bad:
+                    failures.append(bad)
+    assert not failures, f"{len(failures)} layouts differ:\n" + "\n".join(failures[:6])
+
+
+@pytest.mark.parametrize("tname", ["l8", "rgb8", "rgb16", "rgba16", "rgbaf32"])
+def test_copy_rows_alignment_matrix(hip, tname):
+    """same-type copies (k_copy_rows): 16 bytes per thread when both bases, pitches and layer offsets are multiples of 16 -- with
+    a ragged last unit when the row is not -- else a byte per thread.  Rows whose length is and is not a multiple of 16, pitches
+    equal to the row / a multiple of 16 above it / an odd number of bytes above it on either side, each side top-down or
+    bottom-up, 1 and 3 layers a multiple of 16 apart and not; rows of more than 4096 bytes span several blocks."""
+    rng = np.random.default_rng(777 + PT[tname])
+    ps = PT_SIZE[PT[tname]]
+    widths = [48, 53, 4096 // ps + 3]
+    assert any(w * ps % 16 == 0 for w in widths) and (ps == 16 or any(w * ps % 16 for w in widths)) and widths[2] * ps > 4096
+    failures = []
+    for w in widths:
+        row = w * ps
+        h = 3 if row > 4096 else 5
+        pitches = (row, _up16(row) + 16, row + 5)
+        assert pitches[2] % 16
+        for sp in pitches:
+            for dp in pitches:
+                for sflip in (False, True):
+                    for dflip in (False, True):
+                        for layers, sgap, dgap in ((1, 0, 0), (3, (-sp * h) % 16 + 16, (-dp * h) % 16 + 32), (3, (-sp * h) % 16 + 16, (-dp * h) % 16 + 23)):
+                            bad = _convert_geometry(hip, rng, tname, tname, w, h, sp, dp, sflip, dflip, layers, sgap, dgap)
+                            if bad:
+                                failures.append(bad)
+    assert not failures, f"{len(failures)} layouts differ:\n" + "\n".join(failures[:6])
+
+
+@pytest.mark.parametrize("src,dst", [("rgba8", "rgb8"), ("rgbf32", "rgba16")])
+def test_layered_wide_padded(hip, src, dst):
+    """3 layers of wide rows with padded pitches (not gapless: rows and layers are indexed, nothing collapses), the layers a
+    multiple of 16 apart (the vector kernel), 4 bytes off and 1 byte off (the byte kernel for what 4 or 1 misaligns); every
+    layer against the oracle, the gaps between the layers and around them unchanged"""
+    rng = np.random.default_rng(888 + PT[src])
+    ss, ds = PT_SIZE[PT[src]], PT_SIZE[PT[dst]]
+    failures = []
+    for w in (1100, 2053):
+        sp, dp = _up16(w * ss) + 16, _up16(w * ds) + 16
+        for h in (4, 1):
+            for sgap, dgap in ((32, 48), (32, 36), (20, 48), (33, 48), (32, 17), (0, 0)):
+                for flip in (False, True):
+                    bad = _convert_geometry(hip, rng, src, dst, w, h, sp, dp, flip, flip, 3, sgap, dgap)
+                    if bad:
+                        failures.append(bad)
+    assert not failures, f"{len(failures)} layouts differ:\n" + "\n".join(failures[:6])
