@@ -28,7 +28,7 @@ extern(C)
     enum { GAMUT_JPGD_GRAYSCALE = 0, GAMUT_JPGD_YH1V1, GAMUT_JPGD_YH2V1, GAMUT_JPGD_YH1V2, GAMUT_JPGD_YH2V2 }
     enum { GAMUT_HIP_INFLATE_E_BLOCK_TYPE = 1, GAMUT_HIP_INFLATE_E_STORED, GAMUT_HIP_INFLATE_E_LENGTHS, GAMUT_HIP_INFLATE_E_CODE,
            GAMUT_HIP_INFLATE_E_DISTANCE, GAMUT_HIP_INFLATE_E_INPUT }
-    enum { GAMUT_HIP_FORMAT_UNKNOWN = -1, GAMUT_HIP_FORMAT_JPEG = 0, GAMUT_HIP_FORMAT_PNG = 1, GAMUT_HIP_FORMAT_QOI = 2 }
+    enum { GAMUT_HIP_FORMAT_UNKNOWN = -1, GAMUT_HIP_FORMAT_JPEG = 0, GAMUT_HIP_FORMAT_PNG = 1, GAMUT_HIP_FORMAT_QOI = 2, GAMUT_HIP_FORMAT_BMP = 7 }
     enum GAMUT_HIP_QOI_SLACK = 160;
     enum GAMUT_HIP_COMM_ID_BYTES = 128;
 
@@ -155,6 +155,19 @@ extern(C)
                                             int count, const(long)* out_offset, ubyte* out_, long* out_len, int* status_host,
                                             void* stream);
 
+    // BMP: stbi__bmp_load / write_bmp on the GPU (codecs/stbdec.d:2112-2512, codecs/bmpenc.d, plugins/bmp.d)
+    struct gamut_hip_bmp_info { int width, height, bpp, header_size, compression, channels_in_file, top_down, pixel_offset, palette_size;
+                                uint mask_r, mask_g, mask_b, mask_a; float pixels_per_meter_x, pixels_per_meter_y, pixel_aspect_ratio; }
+    int   gamut_hip_bmp_read_header(const(ubyte)* data, size_t len, gamut_hip_bmp_info* info);
+    int   gamut_hip_bmp_decode_batch_device(const(ubyte*)* data, const(size_t)* len, int count, int req_comp, const(long)* out_offset,
+                                            ubyte* out_, gamut_hip_bmp_info* info, int* status_host, void* stream);
+    float gamut_hip_bmp_last_decode_kernel_ms();
+    long  gamut_hip_bmp_encode_bound(int width, int height, int comp);
+    int   gamut_hip_bmp_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(int)* width, const(int)* height,
+                                            const(int)* comp, const(int)* ppm_x, const(int)* ppm_y, int count, const(long)* out_offset,
+                                            ubyte* out_, long* out_len, int* status_host, void* stream);
+    void* gamut_hip_bmp_write_to_mem(const(void)* data, int pitch, int w, int h, int comp, int ppm_x, int ppm_y, int* out_len);
+
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }
     int gamut_hip_identify_format(const(ubyte)* data, size_t len);
@@ -186,6 +199,8 @@ extern(C)
     static assert(gamut_hip_png_info.sizeof == 32 && gamut_hip_png_info.width.offsetof == 0 && gamut_hip_png_info.height.offsetof == 4 && gamut_hip_png_info.channels_in_file.offsetof == 8 && gamut_hip_png_info.channels.offsetof == 12 && gamut_hip_png_info.bits.offsetof == 16 && gamut_hip_png_info.pixels_per_meter_x.offsetof == 20 && gamut_hip_png_info.pixels_per_meter_y.offsetof == 24 && gamut_hip_png_info.pixel_aspect_ratio.offsetof == 28);
     static assert(gamut_hip_qoi_desc.sizeof == 12 && gamut_hip_qoi_desc.width.offsetof == 0 && gamut_hip_qoi_desc.height.offsetof == 4 && gamut_hip_qoi_desc.channels.offsetof == 8 && gamut_hip_qoi_desc.colorspace.offsetof == 9);
     static assert(gamut_hip_image_info.sizeof == 20 && gamut_hip_image_info.format.offsetof == 0 && gamut_hip_image_info.width.offsetof == 4 && gamut_hip_image_info.height.offsetof == 8 && gamut_hip_image_info.channels_in_file.offsetof == 12 && gamut_hip_image_info.channels.offsetof == 16);
+    // (the BMP struct's numbers are the ones tests/c/bmp_abi_layout.c prints; tests/test_bmp_cpu.py compares them every run)
+    static assert(64 == gamut_hip_bmp_info.sizeof && 0 == gamut_hip_bmp_info.width.offsetof && 4 == gamut_hip_bmp_info.height.offsetof && 8 == gamut_hip_bmp_info.bpp.offsetof && 12 == gamut_hip_bmp_info.header_size.offsetof && 16 == gamut_hip_bmp_info.compression.offsetof && 20 == gamut_hip_bmp_info.channels_in_file.offsetof && 24 == gamut_hip_bmp_info.top_down.offsetof && 28 == gamut_hip_bmp_info.pixel_offset.offsetof && 32 == gamut_hip_bmp_info.palette_size.offsetof && 36 == gamut_hip_bmp_info.mask_r.offsetof && 40 == gamut_hip_bmp_info.mask_g.offsetof && 44 == gamut_hip_bmp_info.mask_b.offsetof && 48 == gamut_hip_bmp_info.mask_a.offsetof && 52 == gamut_hip_bmp_info.pixels_per_meter_x.offsetof && 56 == gamut_hip_bmp_info.pixels_per_meter_y.offsetof && 60 == gamut_hip_bmp_info.pixel_aspect_ratio.offsetof);
 }
 
 // ================================================================================================================

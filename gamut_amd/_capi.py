@@ -40,6 +40,13 @@ class JpegFrame(C.Structure):
                 ("pixel_aspect_ratio", C.c_float), ("dpi_y", C.c_float)]
 
 
+class BmpInfo(C.Structure):                                    # gamut_hip_bmp_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bpp", C.c_int32), ("header_size", C.c_int32), ("compression", C.c_int32),
+                ("channels_in_file", C.c_int32), ("top_down", C.c_int32), ("pixel_offset", C.c_int32), ("palette_size", C.c_int32),
+                ("mask_r", C.c_uint32), ("mask_g", C.c_uint32), ("mask_b", C.c_uint32), ("mask_a", C.c_uint32),
+                ("pixels_per_meter_x", C.c_float), ("pixels_per_meter_y", C.c_float), ("pixel_aspect_ratio", C.c_float)]
+
+
 class ImageInfo(C.Structure):                                  # gamut_hip_image_info
     _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels_in_file", C.c_int32), ("channels", C.c_int32)]
 
@@ -98,6 +105,13 @@ SIGNATURES = {
     "gamut_hip_png_write_to_mem": (_vp, [_vp, _i, _i, _i, _i, _pi, _i, _i, _i]),
     "gamut_hip_png_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), _pi, _pi, _pi, _pi, _pi, _pi, _i, C.POINTER(_i64), _vp,
                                            C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_bmp_read_header": (_i, [_vp, _sz, C.POINTER(BmpInfo)]),
+    "gamut_hip_bmp_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _i, C.POINTER(_i64), _vp, C.POINTER(BmpInfo), _pi, _vp]),
+    "gamut_hip_bmp_last_decode_kernel_ms": (_f, []),
+    "gamut_hip_bmp_encode_bound": (_i64, [_i, _i, _i]),
+    "gamut_hip_bmp_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), _pi, _pi, _pi, _pi, _pi, _i, C.POINTER(_i64), _vp,
+                                           C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_bmp_write_to_mem": (_vp, [_vp, _i, _i, _i, _i, _i, _i, _pi]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

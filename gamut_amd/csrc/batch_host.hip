@@ -72,6 +72,10 @@ extern "C" int gamut_hip_identify_format(const uint8_t* b, size_t len)
     if (b && len >= 2 && b[0] == 0xFF && b[1] == 0xD8) return GAMUT_HIP_FORMAT_JPEG;        // detectJPEG plugins/jpeg.d:106-110
     if (b && len >= 8 && !memcmp(b, png, 8)) return GAMUT_HIP_FORMAT_PNG;                   // detectPNG plugins/png.d:165-169
     if (b && len >= 4 && !memcmp(b, "qoif", 4)) return GAMUT_HIP_FORMAT_QOI;                // detectQOI plugins/qoi.d:143-147
+    if (b && len >= 18 && b[0] == 'B' && b[1] == 'M') {                                     // detectBMP plugins/bmp.d:45-82
+        const uint32_t ds = (uint32_t)b[14] | (uint32_t)b[15] << 8 | (uint32_t)b[16] << 16 | (uint32_t)b[17] << 24;
+        if (ds == 12 || ds == 40 || ds == 52 || ds == 56 || ds == 108 || ds == 124) return GAMUT_HIP_FORMAT_BMP;
+    }
     return GAMUT_HIP_FORMAT_UNKNOWN;
 }
 
@@ -88,7 +92,7 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
     (void)hipGetDevice(&dev);
     try {
         // the files by format, in the caller's order
-        std::vector<int> idx[3];
+        std::vector<int> idx[3], bmp_idx;
         std::vector<int> own_status;
         int* hst = status_host;
         if (!hst) { own_status.assign((size_t)count, GAMUT_HIP_OK); hst = own_status.data(); }
@@ -97,7 +101,8 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
             const int f = gamut_hip_identify_format(data[i], len[i]);
             info[i].format = f;
             hst[i] = f < 0 ? GAMUT_HIP_ERR_UNSUPPORTED : GAMUT_HIP_OK;                       // kStrImageFormatUnidentified (image.d:1758-1762)
-            if (f >= 0) idx[f].push_back(i);
+            if (f == GAMUT_HIP_FORMAT_BMP) bmp_idx.push_back(i);
+            else if (f >= 0) idx[f].push_back(i);
         }
         struct Leg {
             std::vector<const uint8_t*> ptr; std::vector<size_t> len; std::vector<int> isize; std::vector<int64_t> off; std::vector<int> st;
@@ -148,6 +153,32 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
             if (r.rc != GAMUT_HIP_OK) snprintf(r.msg, sizeof(r.msg), "%s", gamut_hip_last_error());
             if (own_stream) (void)hipStreamSynchronize(ls);                                   // (the per-format calls return when their pixels are in place)
         };
+        // The BMP files, if any: a fourth, short leg (one launch) on a stream of its own behind `stream`, run from this thread once the
+        // workers have their jobs and the JPEG leg is done -- before the workers are waited for.  A batch without BMP files never
+        // comes here.
+        LegResult bres;
+        std::vector<gamut_hip_bmp_info> bi(bmp_idx.size()); std::vector<int> bst(bmp_idx.size(), GAMUT_HIP_OK);
+        auto run_bmp = [&](bool own_stream) {
+            if (bmp_idx.empty()) return;
+            const size_t n = bmp_idx.size();
+            std::vector<const uint8_t*> bptr(n); std::vector<size_t> blen(n); std::vector<int64_t> boff(n);
+            for (size_t k = 0; k < n; ++k) { const int i = bmp_idx[k]; bptr[k] = data[i]; blen[k] = len[i]; boff[k] = out_offset[i]; }
+            hipStream_t ls = st;
+            if (own_stream) {
+                static thread_local PerDevice<hipStream_t> bmp_stream_pd;
+                hipStream_t& s = bmp_stream_pd.cur();
+                if ((!s && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) || hipStreamWaitEvent(s, fork, 0) != hipSuccess) {
+                    bres.rc = GAMUT_HIP_ERR_HIP; snprintf(bres.msg, sizeof(bres.msg), "decode_batch_device: stream setup of the BMP leg failed"); return;
+                }
+                ls = s;
+            }
+            bres.rc = gamut_hip_bmp_decode_batch_device(bptr.data(), blen.data(), (int)n, req_comps, boff.data(), out, bi.data(), bst.data(), ls);
+            if (bres.rc != GAMUT_HIP_OK) {
+                const char* m = gamut_hip_last_error();                                           // "image k: ..." with k counted inside the leg: keep what follows
+                if (!strncmp(m, "image ", 6) && strstr(m, ": ")) m = strstr(m, ": ") + 2;
+                snprintf(bres.msg, sizeof(bres.msg), "%s", m);
+            }
+        };
         // The longest legs first on the workers (PNG: inflate-bound, QOI: PCIe-bound), JPEG on the calling thread.  When another
         // thread's mixed batch holds the workers, the legs run one after the other here: same results.
         static const bool serial = [] { const char* e = getenv("GAMUT_HIP_MIXED_SERIAL"); return e && *e && atoi(e) != 0; }();     // measurements
@@ -166,8 +197,11 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
                 ++jobs.n;                                                                     // only what was really handed over is waited for
             }
             run_leg(GAMUT_HIP_FORMAT_JPEG, true);
+            try { run_bmp(true); }                                                            // (the workers still use this frame: nothing may leave it before `jobs` has waited)
+            catch (...) { bres.rc = GAMUT_HIP_ERR_OUT_OF_MEMORY; snprintf(bres.msg, sizeof(bres.msg), "decode_batch_device: out of host memory in the BMP leg"); }
         } else {
             for (int f = 0; f < 3; ++f) run_leg(f, false);
+            run_bmp(false);
         }
         (void)hipSetDevice(dev);
 
@@ -187,14 +221,21 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
             info[i].width = (int)f.width; info[i].height = (int)f.height; info[i].channels_in_file = f.channels; info[i].channels = req_comps;
             hst[i] = leg[GAMUT_HIP_FORMAT_QOI].st[k];
         }
+        for (size_t k = 0; k < bmp_idx.size(); ++k) {
+            const int i = bmp_idx[k];
+            info[i].width = bi[k].width; info[i].height = bi[k].height; info[i].channels_in_file = bi[k].channels_in_file; info[i].channels = req_comps;
+            hst[i] = bst[k];
+        }
         // a failure that is not a per-file verdict (allocation, HIP) is the call's; otherwise the lowest-numbered failing file's
+        if (bres.rc != GAMUT_HIP_OK && bres.rc != GAMUT_HIP_ERR_DECODE && bres.rc != GAMUT_HIP_ERR_INVALID_ARG) return set_error(bres.rc, "%s", bres.msg);
         for (int f = 0; f < 3; ++f)
             if (res[f].rc != GAMUT_HIP_OK && res[f].rc != GAMUT_HIP_ERR_DECODE && res[f].rc != GAMUT_HIP_ERR_UNSUPPORTED && res[f].rc != GAMUT_HIP_ERR_INVALID_ARG)
                 return set_error(res[f].rc, "%s", res[f].msg);
         for (int i = 0; i < count; ++i) {
             if (hst[i] == GAMUT_HIP_OK) continue;
             const int f = info[i].format;
-            if (f < 0) return set_error(GAMUT_HIP_ERR_UNSUPPORTED, "image %d: format not identified (JPEG, PNG and QOI files are decoded)", i);
+            if (f < 0) return set_error(GAMUT_HIP_ERR_UNSUPPORTED, "image %d: format not identified (JPEG, PNG, QOI and BMP files are decoded)", i);
+            if (f == GAMUT_HIP_FORMAT_BMP) return set_error(hst[i], "image %d: %s", i, bres.msg[0] ? bres.msg : "decoding failed");
             return set_error(hst[i], "image %d: %s", i, res[f].msg[0] ? res[f].msg : "decoding failed");
         }
         return GAMUT_HIP_OK;

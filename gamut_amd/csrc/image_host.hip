@@ -415,6 +415,35 @@ struct gamut_image {
         _layoutConstraints = 0;
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);
     }
+    void loadBMP(const uint8_t* bytes, size_t len, int flags)                               // plugins/bmp.d:85-163
+    {
+        int requested = computeRequestedImageComponents(flags);
+        if (requested == 0) { error(kStrInvalidFlags); return; }
+        if (requested == -1) requested = 0;
+        gamut_hip_bmp_info hd, info;
+        if (gamut_hip_bmp_read_header(bytes, len, &hd) != GAMUT_HIP_OK) { error(kStrImageDecodingFailed); return; }
+        const int comps = requested ? requested : hd.channels_in_file;
+        const size_t nbytes = (size_t)hd.width * hd.height * comps;
+        // the decode is the GPU's either way; a host image gets the pixels copied back from a staging allocation
+        uint8_t* dev = dmalloc(nbytes);
+        const int64_t zero = 0; int st = 0;
+        if (!dev || gamut_hip_bmp_decode_batch_device(&bytes, &len, 1, requested, &zero, dev, &info, &st, nullptr) != GAMUT_HIP_OK) {
+            if (dev) (void)hipFree(dev);
+            error(kStrImageDecodingFailed); return;
+        }
+        uint8_t* decoded = dev;
+        if (!_device) {
+            decoded = (uint8_t*)malloc(nbytes ? nbytes : 1);
+            const bool ok = decoded && gamut_hip_memcpy_d2h(decoded, dev, nbytes, nullptr) == GAMUT_HIP_OK && gamut_hip_stream_synchronize(nullptr) == GAMUT_HIP_OK;
+            (void)hipFree(dev);
+            if (!ok) { free(decoded); error(kStrImageDecodingFailed); return; }
+        }
+        if (!imageIsValidSize(1, info.width, info.height)) { error(kStrImageTooLarge); release(decoded); return; }
+        static const int t8[5] = { -1, GAMUT_PIXEL_l8, GAMUT_PIXEL_la8, GAMUT_PIXEL_rgb8, GAMUT_PIXEL_rgba8 };
+        adopt(decoded, info.width, info.height, t8[comps], comps, info.pixel_aspect_ratio == -1 ? -1.0f : info.pixel_aspect_ratio,
+              info.pixels_per_meter_y == -1 ? -1.0f : info.pixels_per_meter_y / 39.37007874f);          // :134-135, convertInchesToMeters
+        convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);
+    }
 };
 
 static int identify(const uint8_t* b, size_t len)
@@ -423,6 +452,7 @@ static int identify(const uint8_t* b, size_t len)
     if (b && len >= 2 && b[0] == 0xFF && b[1] == 0xD8) return GAMUT_FORMAT_JPEG;            // detectJPEG plugins/jpeg.d:106-110
     if (b && len >= 8 && !memcmp(b, png, 8)) return GAMUT_FORMAT_PNG;                       // detectPNG plugins/png.d:165-169
     if (b && len >= 4 && !memcmp(b, "qoif", 4)) return GAMUT_FORMAT_QOI;                    // detectQOI plugins/qoi.d:144-148
+    if (gamut_hip_identify_format(b, len) == GAMUT_HIP_FORMAT_BMP) return GAMUT_FORMAT_BMP;  // detectBMP plugins/bmp.d:45-82
     return GAMUT_FORMAT_unknown;
 }
 
@@ -471,6 +501,7 @@ int gamut_image_load_from_memory(gamut_image* img, const uint8_t* bytes, size_t 
     case GAMUT_FORMAT_JPEG: img->loadJPEG(bytes, len, flags); break;
     case GAMUT_FORMAT_PNG:  img->loadPNG(bytes, len, flags); break;
     case GAMUT_FORMAT_QOI:  img->loadQOI(bytes, len, flags); break;
+    case GAMUT_FORMAT_BMP:  img->loadBMP(bytes, len, flags); break;
     default: img->error(kStrImageFormatUnidentified); break;
     }
     return img->isValid();
@@ -728,6 +759,62 @@ int gamut_image_save_png_to_file(gamut_image* img, const char* path, int flags)
     if (!path) return 0;
     size_t n = 0;
     uint8_t* enc = gamut_image_save_png_to_memory(img, flags, &n);
+    if (!enc) return 0;
+    FILE* f = fopen(path, "wb");
+    bool ok = f && fwrite(enc, 1, n, f) == n;
+    if (f && fclose(f) != 0) ok = false;
+    free(enc);
+    return ok;
+}
+
+// saveBMP (plugins/bmp.d:166-194) + write_bmp's density fields (bmpenc.d:63-74): rgb8 / rgba8, one layer, 1..32767 each way
+static uint8_t* save_bmp(gamut_image* img, size_t* len)
+{
+    const int comp = img->_type == GAMUT_PIXEL_rgb8 ? 3 : img->_type == GAMUT_PIXEL_rgba8 ? 4 : 0;
+    const int w = img->_width, h = img->_height;
+    if (!comp || img->_layerCount != 1 || gamut_hip_bmp_encode_bound(w, h, comp) == 0) return nullptr;
+    // pixelsPerMeterY = convertMetersToInches(dotsPerInchY), X through the aspect ratio (image.d:314-361)
+    int ppm_x = 0, ppm_y = 0;
+    if (img->_resolutionY != -1) {
+        ppm_y = (int)roundf(img->_resolutionY * 39.37007874f);
+        if (img->_pixelAspectRatio != -1) ppm_x = (int)roundf(img->_resolutionY * img->_pixelAspectRatio * 39.37007874f);
+    }
+    if (!img->_device) {
+        int n = 0;
+        uint8_t* r = (uint8_t*)gamut_hip_bmp_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, ppm_x, ppm_y, &n);
+        if (r) *len = (size_t)n;
+        return r;
+    }
+    const size_t bound = (size_t)gamut_hip_bmp_encode_bound(w, h, comp);
+    hipStream_t st = thread_stream();
+    static thread_local PerDevice<DeviceScratch> out_pd;
+    uint8_t* d = nullptr;
+    try { d = (uint8_t*)out_pd.cur().get(bound, st); } catch (...) { d = nullptr; }
+    if (!d) return nullptr;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    const int32_t W = w, H = h, Cc = comp, PX = ppm_x, PY = ppm_y;
+    if (gamut_hip_bmp_encode_batch_device(&src, &pitch, &W, &H, &Cc, &PX, &PY, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
+    uint8_t* r = (uint8_t*)malloc((size_t)n);
+    if (!r) return nullptr;
+    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); free(r); return nullptr;
+    }
+    *len = (size_t)n;
+    return r;
+}
+
+uint8_t* gamut_image_save_bmp_to_memory(gamut_image* img, int flags, size_t* len)
+{
+    (void)flags;                                               // saveBMP ignores them
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
+    return save_bmp(img, len);
+}
+int gamut_image_save_bmp_to_file(gamut_image* img, const char* path, int flags)
+{
+    if (!path) return 0;
+    size_t n = 0;
+    uint8_t* enc = gamut_image_save_bmp_to_memory(img, flags, &n);
     if (!enc) return 0;
     FILE* f = fopen(path, "wb");
     bool ok = f && fwrite(enc, 1, n, f) == n;

@@ -408,6 +408,55 @@ int     gamut_hip_png_encode_batch_device(const uint8_t* const* src, const int64
                                           const int32_t* force_filter, const int32_t* level, int count, const int64_t* out_offset,
                                           uint8_t* out, int64_t* out_len, int* status_host, void* stream);
 
+/* ---- BMP (stbi__bmp_load, codecs/stbdec.d:2112-2512; write_bmp, codecs/bmpenc.d; plugins/bmp.d) ---------------------------------
+ * Decode: every pixel what stbi__bmp_load gives, bit for bit: 1 / 4 / 8-bit palette, 16 / 32-bit with masks, 24-bit and plain 32-bit,
+ * header sizes 12 / 40 / 56 / 108 / 124, bottom-up and top-down, no RLE (the reference refuses it); the all-alpha-zero rule of 32-bit
+ * BI_RGB files (:2137, :2439-2443) included.  Bytes past the end of a file read as zero, as the reference's reader hands them out.
+ * Deliberate deviations: a palette index >= the palette size gives (0, 0, 0) (the reference reads uninitialised memory); a negative
+ * palette size and a width or height of 0 are refused.
+ * (Declared typedef-first: the layout of this struct is pinned by tests/c/bmp_abi_layout.c and tests/test_bmp_cpu.py.) */
+typedef struct gamut_hip_bmp_info gamut_hip_bmp_info;
+struct gamut_hip_bmp_info {
+    int32_t  width, height;         /* height as a positive number */
+    int32_t  bpp, header_size, compression;
+    int32_t  channels_in_file;      /* what stbi reports as *comp: 3 or 4 */
+    int32_t  top_down;              /* 1: the file's first row is the top one (negative biHeight) */
+    int32_t  pixel_offset;          /* where the reference starts to read pixels (bmp_host.hip) */
+    int32_t  palette_size;          /* entries, 0 for 16 / 24 / 32 bits */
+    uint32_t mask_r, mask_g, mask_b, mask_a;
+    float    pixels_per_meter_x, pixels_per_meter_y, pixel_aspect_ratio;   /* -1 when unknown (values <= 1 count as unknown) */
+};
+/* the header alone (host, no GPU needed): the reference's verdict on the file, GAMUT_HIP_ERR_DECODE when it would refuse it */
+int gamut_hip_bmp_read_header(const uint8_t* data, size_t len, gamut_hip_bmp_info* info);
+/* `count` BMP files in host memory -> tight rows of width * comps bytes at out + out_offset[i] (device); req_comp as in stbi_load:
+ * 0 (as in the file), 1, 2, 3 or 4.  One launch for the whole batch, whatever the files' geometries and depths.  info[i] /
+ * status_host[i] (either may be NULL) per file; a refused file gets its status and does not disturb the others; returns the status
+ * of the lowest-numbered refused file.  Nothing outside an image's width * height * comps bytes is written.  Returns when the
+ * pixels are in place. */
+int gamut_hip_bmp_decode_batch_device(const uint8_t* const* data, const size_t* len, int count, int req_comp,
+                                      const int64_t* out_offset, uint8_t* out, gamut_hip_bmp_info* info, int* status_host, void* stream);
+/* measurements: with the environment variable GAMUT_HIP_BMP_TIMING=1 the decode call brackets its kernels (not the upload) with events;
+ * this returns the GPU milliseconds of the calling thread's last decode call, -1 when timing is off or nothing was decoded */
+float gamut_hip_bmp_last_decode_kernel_ms(void);
+/* Encode: byte for byte write_bmp (bmpenc.d:25-114) -- a BITMAPV4 header of 122 bytes, rows bottom-up, B and R swapped; comp 3
+ * (24 bits, BI_RGB) or 4 (32 bits, BI_BITFIELDS with the four masks), 1 <= width, height <= 32767 (plugins/bmp.d:174-189).
+ * Deliberate deviation: the 0..3 pad bytes of a 24-bit row, which the reference writes from an uninitialised buffer, are zero.
+ * The file length 122 + height * ((width * comp + 3) & ~3), or 0 when saveBMP / write_bmp would refuse the shape. */
+int64_t gamut_hip_bmp_encode_bound(int width, int height, int comp);
+/* batch: image i is read from DEVICE memory at src[i] (rows src_pitch[i] apart, negative allowed, any alignment) and written to
+ * out + out_offset[i] (device, any alignment), which must have gamut_hip_bmp_encode_bound(...) bytes; nothing outside
+ * [out_offset[i], out_offset[i] + out_len[i]) is written.  ppm_x / ppm_y: biXPelsPerMeter / biYPelsPerMeter per image, either
+ * may be NULL (0).  out_len[i] / status_host[i] (host arrays; status_host may be NULL): a refused image (or a NULL src[i], a
+ * negative out_offset[i]) gets GAMUT_HIP_ERR_INVALID_ARG and out_len 0, the others are still encoded, and the call returns the
+ * status of the lowest-numbered refused image.  Returns when the encode has finished. */
+int     gamut_hip_bmp_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const int32_t* width,
+                                          const int32_t* height, const int32_t* comp, const int32_t* ppm_x, const int32_t* ppm_y,
+                                          int count, const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host,
+                                          void* stream);
+/* host pixels (rows `pitch` bytes apart, negative allowed) through pinned staging -> malloc'd file of *out_len bytes, or NULL on
+ * refusal (see last_error) */
+void*   gamut_hip_bmp_write_to_mem(const void* data, int pitch, int w, int h, int comp, int ppm_x, int ppm_y, int* out_len);
+
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
  * procedures, a signature test each: plugins/jpeg.d:106-110, png.d:165-169, qoi.d:143-147) picks g_plugins[fif].loadProc
@@ -418,8 +467,11 @@ int     gamut_hip_png_encode_batch_device(const uint8_t* const* src, const int64
  * per-format batch calls run SIDE BY SIDE, each on a stream of its own behind `stream` and on a worker thread of the library: the
  * PNG leg is bound by the inflate kernels while the QOI leg is bound by PCIe, and the JPEG leg is short.  info[i] receives format
  * and geometry, status_host[i] (may be NULL) the file's status (GAMUT_HIP_ERR_UNSUPPORTED: format not identified).  Returns when
- * the pixels are in place; the status of the lowest-numbered failing file, GAMUT_HIP_OK if none. */
-enum { GAMUT_HIP_FORMAT_UNKNOWN = -1, GAMUT_HIP_FORMAT_JPEG = 0, GAMUT_HIP_FORMAT_PNG = 1, GAMUT_HIP_FORMAT_QOI = 2 };
+ * the pixels are in place; the status of the lowest-numbered failing file, GAMUT_HIP_OK if none.
+ * BMP files (detectBMP, plugins/bmp.d:45-82: 'B', 'M' and a known header size at offset 14; tested after the three signatures above)
+ * are a fourth, short leg: gamut_hip_bmp_decode_batch_device on a stream of its own, run from the calling thread once the workers have
+ * their legs and before they are waited for. */
+enum { GAMUT_HIP_FORMAT_UNKNOWN = -1, GAMUT_HIP_FORMAT_JPEG = 0, GAMUT_HIP_FORMAT_PNG = 1, GAMUT_HIP_FORMAT_QOI = 2, GAMUT_HIP_FORMAT_BMP = 7 };
 typedef struct gamut_hip_image_info { int32_t format, width, height, channels_in_file, channels; } gamut_hip_image_info;
 int gamut_hip_identify_format(const uint8_t* data, size_t len);
 int gamut_hip_decode_batch_device(const uint8_t* const* data, const size_t* len, int count, int req_comps,

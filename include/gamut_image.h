@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ImageFormat (types.d:14-28) */
-enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2 };   /* ImageFormat, types.d:14-21 */
+enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_BMP = 7 };   /* ImageFormat, types.d:14-21 */
 
 /* LoadFlags (types.d:139-197) */
 enum {
@@ -124,7 +124,8 @@ int gamut_image_copy_pixels_to_host(gamut_image* img, int layer, void* dst, int6
  * staging.  QOI (gamut_hip_qoi_encode*): rgb8 / rgba8, colorspace sRGB.  JPEG (gamut_hip_jpeg_encode*, byte for byte what
  * stbi_write_jpg_to_func writes): l8 (one component) / rgb8 (three), quality 90, so 4:2:0; rgba8 and every other type are refused
  * as saveJPEG refuses them.  GAMUT_FORMAT_PNG is not dispatched from these two generic entries yet (they return NULL / 0 for it, as
- * for an errored image or an unknown format): PNG is saved through gamut_image_save_png_to_memory / _to_file below.  Flags are
+ * for an errored image or an unknown format): PNG is saved through gamut_image_save_png_to_memory / _to_file below.  Neither is
+ * GAMUT_FORMAT_BMP (7): BMP is saved through gamut_image_save_bmp_to_memory / _to_file below.  Flags are
  * ignored here (as both plugins do).  The image's state and error are left as they were. */
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len);   /* image.d:966-980; NULL (and *len = 0) on refusal */
 int      gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags); /* image.d:953-958; 1 on success */
@@ -142,6 +143,11 @@ enum {
 };
 uint8_t* gamut_image_save_png_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
 int      gamut_image_save_png_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
+/* saveBMP (plugins/bmp.d:166-194; gamut_hip_bmp_*): rgb8 / rgba8 with one layer, 1 <= width, height <= 32767, every other image
+ * refused; byte for byte write_bmp (bmpenc.d), with biX/YPelsPerMeter = round(pixelsPerMeterX / Y) or 0 when unknown; flags are
+ * ignored as saveBMP ignores them.  The image's state and error are left as they were.  Freed with gamut_free_encoded_image. */
+uint8_t* gamut_image_save_bmp_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
+int      gamut_image_save_bmp_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
 
 #ifdef __cplusplus
 }
