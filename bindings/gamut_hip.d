@@ -168,6 +168,14 @@ extern(C)
                                             ubyte* out_, long* out_len, int* status_host, void* stream);
     void* gamut_hip_bmp_write_to_mem(const(void)* data, int pitch, int w, int h, int comp, int ppm_x, int ppm_y, int* out_len);
 
+    // GIF: GIFDecoder + loadGIF on the GPU, every frame composited into a layer (codecs/gif.d, plugins/gif.d:57-103); decode only
+    struct gamut_hip_gif_info { int width, height, layers, is_gif89; float pixel_aspect_ratio, fps; }
+    int   gamut_hip_gif_read_header(const(ubyte)* data, size_t len, gamut_hip_gif_info* info);
+    int   gamut_hip_gif_decode_batch_device(const(ubyte*)* data, const(size_t)* len, int count, const(long)* out_offset,
+                                            const(long)* out_capacity, ubyte* out_, gamut_hip_gif_info* info, int* status_host, void* stream);
+    float gamut_hip_gif_last_decode_kernel_ms();
+    float gamut_hip_gif_last_kernel_ms(int which);
+
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }
     int gamut_hip_identify_format(const(ubyte)* data, size_t len);
@@ -201,6 +209,8 @@ extern(C)
     static assert(gamut_hip_image_info.sizeof == 20 && gamut_hip_image_info.format.offsetof == 0 && gamut_hip_image_info.width.offsetof == 4 && gamut_hip_image_info.height.offsetof == 8 && gamut_hip_image_info.channels_in_file.offsetof == 12 && gamut_hip_image_info.channels.offsetof == 16);
     // (the BMP struct's numbers are the ones tests/c/bmp_abi_layout.c prints; tests/test_bmp_cpu.py compares them every run)
     static assert(64 == gamut_hip_bmp_info.sizeof && 0 == gamut_hip_bmp_info.width.offsetof && 4 == gamut_hip_bmp_info.height.offsetof && 8 == gamut_hip_bmp_info.bpp.offsetof && 12 == gamut_hip_bmp_info.header_size.offsetof && 16 == gamut_hip_bmp_info.compression.offsetof && 20 == gamut_hip_bmp_info.channels_in_file.offsetof && 24 == gamut_hip_bmp_info.top_down.offsetof && 28 == gamut_hip_bmp_info.pixel_offset.offsetof && 32 == gamut_hip_bmp_info.palette_size.offsetof && 36 == gamut_hip_bmp_info.mask_r.offsetof && 40 == gamut_hip_bmp_info.mask_g.offsetof && 44 == gamut_hip_bmp_info.mask_b.offsetof && 48 == gamut_hip_bmp_info.mask_a.offsetof && 52 == gamut_hip_bmp_info.pixels_per_meter_x.offsetof && 56 == gamut_hip_bmp_info.pixels_per_meter_y.offsetof && 60 == gamut_hip_bmp_info.pixel_aspect_ratio.offsetof);
+    // (the GIF struct's numbers are the ones tests/c/gif_abi_layout.c prints; tests/test_gif_cpu.py compares them every run)
+    static assert(24 == gamut_hip_gif_info.sizeof && 0 == gamut_hip_gif_info.width.offsetof && 4 == gamut_hip_gif_info.height.offsetof && 8 == gamut_hip_gif_info.layers.offsetof && 12 == gamut_hip_gif_info.is_gif89.offsetof && 16 == gamut_hip_gif_info.pixel_aspect_ratio.offsetof && 20 == gamut_hip_gif_info.fps.offsetof);
 }
 
 // ================================================================================================================

@@ -47,6 +47,11 @@ class BmpInfo(C.Structure):                                    # gamut_hip_bmp_i
                 ("pixels_per_meter_x", C.c_float), ("pixels_per_meter_y", C.c_float), ("pixel_aspect_ratio", C.c_float)]
 
 
+class GifInfo(C.Structure):                                    # gamut_hip_gif_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("layers", C.c_int32), ("is_gif89", C.c_int32),
+                ("pixel_aspect_ratio", C.c_float), ("fps", C.c_float)]
+
+
 class ImageInfo(C.Structure):                                  # gamut_hip_image_info
     _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels_in_file", C.c_int32), ("channels", C.c_int32)]
 
@@ -112,6 +117,10 @@ SIGNATURES = {
     "gamut_hip_bmp_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), _pi, _pi, _pi, _pi, _pi, _i, C.POINTER(_i64), _vp,
                                            C.POINTER(_i64), _pi, _vp]),
     "gamut_hip_bmp_write_to_mem": (_vp, [_vp, _i, _i, _i, _i, _i, _i, _pi]),
+    "gamut_hip_gif_read_header": (_i, [_vp, _sz, C.POINTER(GifInfo)]),
+    "gamut_hip_gif_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, C.POINTER(_i64), C.POINTER(_i64), _vp, C.POINTER(GifInfo), _pi, _vp]),
+    "gamut_hip_gif_last_decode_kernel_ms": (_f, []),
+    "gamut_hip_gif_last_kernel_ms": (_f, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

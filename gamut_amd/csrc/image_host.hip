@@ -444,6 +444,41 @@ struct gamut_image {
               info.pixels_per_meter_y == -1 ? -1.0f : info.pixels_per_meter_y / 39.37007874f);          // :134-135, convertInchesToMeters
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);
     }
+    // Layers of tight top-down rgba8 rows (device memory) into the image's own storage, whatever pitch and layer offset its constraints gave it
+    bool fillLayersFromDevice(const uint8_t* dev, size_t layerBytes, size_t rowBytes)
+    {
+        if (!layerBytes || !_layerCount) return true;
+        if (_device)                                                                         // one launch of the same-type scanline copy (k_copy_rows)
+            return gamut_hip_scanlines_convert_device(_type, dev, (int64_t)rowBytes, (int64_t)layerBytes, _type, _data, _pitch, _layerOffset,
+                                                      _width, _height, _layerCount, nullptr) == GAMUT_HIP_OK &&
+                   gamut_hip_stream_synchronize(nullptr) == GAMUT_HIP_OK;
+        std::vector<uint8_t> host(layerBytes * (size_t)_layerCount);
+        if (gamut_hip_memcpy_d2h(host.data(), dev, host.size(), nullptr) != GAMUT_HIP_OK || gamut_hip_stream_synchronize(nullptr) != GAMUT_HIP_OK) return false;
+        for (int l = 0; l < _layerCount; ++l)
+            for (int y = 0; y < _height; ++y)
+                memcpy(_data + (ptrdiff_t)l * _layerOffset + (ptrdiff_t)y * _pitch, host.data() + (size_t)l * layerBytes + (size_t)y * rowBytes, rowBytes);
+        return true;
+    }
+    void loadGIF(const uint8_t* bytes, size_t len, int flags)                               // plugins/gif.d:57-103
+    {
+        gamut_hip_gif_info hd, info;
+        if (gamut_hip_gif_read_header(bytes, len, &hd) != GAMUT_HIP_OK) { error(kStrImageDecodingFailed); return; }     // decoder.open: host only
+        // createLayeredNoInit(width, height, numLayers, rgba8, cast(LayoutConstraints) flags) :77-81
+        if (!createLayered(hd.width, hd.height, hd.layers, GAMUT_PIXEL_rgba8, flags & 0xFFFF, false)) return;
+        _resolutionY = -1.0f; _pixelAspectRatio = hd.pixel_aspect_ratio;                   // :70-71
+        const size_t layerBytes = (size_t)hd.width * hd.height * 4, nbytes = layerBytes * (size_t)hd.layers;
+        if (nbytes) {
+            // the decode is the GPU's either way: straight into a device image whose layers are tight, else through a staging allocation
+            const bool direct = _device && _pitch == hd.width * 4 && (hd.layers <= 1 || (size_t)_layerOffset == layerBytes);
+            uint8_t* dev = direct ? _data : dmalloc(nbytes);
+            const int64_t zero = 0, cap = (int64_t)nbytes; int st = 0;
+            bool ok = dev && gamut_hip_gif_decode_batch_device(&bytes, &len, 1, &zero, &cap, dev, &info, &st, nullptr) == GAMUT_HIP_OK;
+            if (ok && !direct) ok = fillLayersFromDevice(dev, layerBytes, (size_t)hd.width * 4);
+            if (dev && !direct) (void)hipFree(dev);
+            if (!ok) { cleanupBitmapIfOwned(); error(kStrImageDecodingFailed); return; }
+        }
+        convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);                           // :102, over all layers
+    }
 };
 
 static int identify(const uint8_t* b, size_t len)
@@ -452,6 +487,7 @@ static int identify(const uint8_t* b, size_t len)
     if (b && len >= 2 && b[0] == 0xFF && b[1] == 0xD8) return GAMUT_FORMAT_JPEG;            // detectJPEG plugins/jpeg.d:106-110
     if (b && len >= 8 && !memcmp(b, png, 8)) return GAMUT_FORMAT_PNG;                       // detectPNG plugins/png.d:165-169
     if (b && len >= 4 && !memcmp(b, "qoif", 4)) return GAMUT_FORMAT_QOI;                    // detectQOI plugins/qoi.d:144-148
+    if (b && len >= 6 && (!memcmp(b, "GIF87a", 6) || !memcmp(b, "GIF89a", 6))) return GAMUT_FORMAT_GIF;   // detectGIF plugins/gif.d:42-53
     if (gamut_hip_identify_format(b, len) == GAMUT_HIP_FORMAT_BMP) return GAMUT_FORMAT_BMP;  // detectBMP plugins/bmp.d:45-82
     return GAMUT_FORMAT_unknown;
 }
@@ -502,6 +538,7 @@ int gamut_image_load_from_memory(gamut_image* img, const uint8_t* bytes, size_t 
     case GAMUT_FORMAT_PNG:  img->loadPNG(bytes, len, flags); break;
     case GAMUT_FORMAT_QOI:  img->loadQOI(bytes, len, flags); break;
     case GAMUT_FORMAT_BMP:  img->loadBMP(bytes, len, flags); break;
+    case GAMUT_FORMAT_GIF:  img->loadGIF(bytes, len, flags); break;
     default: img->error(kStrImageFormatUnidentified); break;
     }
     return img->isValid();

@@ -457,6 +457,44 @@ int     gamut_hip_bmp_encode_batch_device(const uint8_t* const* src, const int64
  * refusal (see last_error) */
 void*   gamut_hip_bmp_write_to_mem(const void* data, int pitch, int w, int h, int comp, int ppm_x, int ppm_y, int* out_len);
 
+/* ---- GIF (GIFDecoder, codecs/gif.d; loadGIF, plugins/gif.d:57-103) --------------------------------------------------------------
+ * Decode only.  Every frame of the file, composited as the reference composites it (its disposal rules, its persistent GCE state --
+ * also from the counting pass of `open` into the decoding pass --, its pixel stepping for interlaced, overhanging and zero-sized
+ * frames, its LZW verdicts), as `layers` tight rgba8 images of width x height.
+ * Deliberate deviations (in each the reference reads or writes memory it does not own): both palette buffers start zeroed, so an
+ * index past every colour table ever read gives an undrawn pixel; a frame with neither a local nor a global colour table is refused;
+ * a frame with frameX + max(frameW, 1) > width is refused (one overhanging the BOTTOM is not: its rows are dropped as in the
+ * reference); a screen of more than 2^29 - 1 pixels is refused.
+ * (Declared typedef-first: the layout of this struct is pinned by tests/c/gif_abi_layout.c and tests/test_gif_cpu.py.) */
+typedef struct gamut_hip_gif_info gamut_hip_gif_info;
+struct gamut_hip_gif_info {
+    int32_t width, height;          /* the logical screen */
+    int32_t layers;                 /* frames in the file; 0 is a valid file */
+    int32_t is_gif89;
+    float   pixel_aspect_ratio;     /* (byte + 15) / 64, -1 when the byte is 0 */
+    float   fps;                    /* layers * 1000 / sum of the frame durations in ms (100 for a delay of 0 or 1, else delay * 10); 10 when the sum is 0 */
+};
+/* host only, no GPU needed: the whole verdict of GIFDecoder.open -- the container and every LZW code of every frame -- with the
+ * deviations above; GAMUT_HIP_ERR_DECODE where the file is refused (info is then zeroed, pixel_aspect_ratio -1) */
+int gamut_hip_gif_read_header(const uint8_t* data, size_t len, gamut_hip_gif_info* info);
+/* `count` GIF files in host memory; layer l of file i goes, as tight rgba8 rows, to out + out_offset[i] + l * width * height * 4
+ * (device).  out_capacity[i]: the bytes file i may use; a file whose layers * width * height * 4 exceed it gets
+ * GAMUT_HIP_ERR_INVALID_ARG (info[i] then tells what it needs; the test is made on what the container claims, before the raster is
+ * looked at).  One LZW launch (a wave per frame) and one compositing launch for
+ * the whole batch.  info[i] / status_host[i] (either may be NULL) per file; a refused file gets its status, leaves its slot
+ * untouched and does not disturb the others; returns the status of the lowest-numbered refused file.  The raster verdict comes
+ * from the LZW kernel's status words, not from the host's code walk.  Nothing outside a file's layers * width * height * 4 bytes is
+ * written.  The files go up through pinned staging; returns when the pixels are in place. */
+int gamut_hip_gif_decode_batch_device(const uint8_t* const* data, const size_t* len, int count, const int64_t* out_offset,
+                                      const int64_t* out_capacity, uint8_t* out, gamut_hip_gif_info* info, int* status_host, void* stream);
+/* measurements: with the environment variable GAMUT_HIP_GIF_TIMING=1 the decode call brackets its kernels (not the upload) with events;
+ * this returns the GPU milliseconds of the calling thread's last decode call (both kernels), -1 when timing is off or nothing was
+ * decoded.  gamut_hip_gif_last_kernel_ms is the same figure split in two, which = 0: the LZW kernel, 1: the compositing kernel.  It
+ * exists because the two kernels are bound differently (a latency chain per frame / the layers' stores) and tools/gif_bench.py
+ * records them apart; a measurement aid like the entry above, not part of the decode interface. */
+float gamut_hip_gif_last_decode_kernel_ms(void);
+float gamut_hip_gif_last_kernel_ms(int which);
+
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
  * procedures, a signature test each: plugins/jpeg.d:106-110, png.d:165-169, qoi.d:143-147) picks g_plugins[fif].loadProc

@@ -9,7 +9,7 @@
  * LoadFlags / LayoutConstraints bits (types.d:139-348).  Pixel storage is host malloc memory exactly as
  * in the reference (the user may disown and free() it); every pixel operation (decode, convertTo) runs
  * on the GPU through gamut_hip_* -- there is no CPU pixel path.
- * Formats: JPEG (baseline), PNG and QOI are read; QOI and JPEG are written (saveToMemory / saveToFile), PNG through savePNG's own entries; other signatures report
+ * Formats: JPEG (baseline), PNG, QOI, BMP and GIF (every frame a layer of an rgba8 image) are read; QOI and JPEG are written (saveToMemory / saveToFile), PNG through savePNG's own entries; other signatures report
  * "Unidentified image format".
  */
 #ifndef GAMUT_IMAGE_H
@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ImageFormat (types.d:14-28) */
-enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_BMP = 7 };   /* ImageFormat, types.d:14-21 */
+enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_GIF = 6, GAMUT_FORMAT_BMP = 7 };   /* ImageFormat, types.d:14-21 */
 
 /* LoadFlags (types.d:139-197) */
 enum {
@@ -53,7 +53,7 @@ int  gamut_compute_requested_image_components(int flags);              /* intern
 int  gamut_valid_load_flags(int flags);                                /* internals/types.d:563-578 */
 int  gamut_layout_constraints_valid(int constraints);                  /* internals/types.d:267-289 */
 int  gamut_layout_constraints_compatible(int newer, int older);        /* internals/types.d:241-264 */
-int  gamut_identify_format_from_memory(const uint8_t* bytes, size_t len);   /* image.d:1038-1061 (JPEG, PNG, QOI) */
+int  gamut_identify_format_from_memory(const uint8_t* bytes, size_t len);   /* image.d:1038-1061 (JPEG, PNG, QOI, GIF, BMP) */
 void gamut_free_image_data(void* mallocArea);                          /* freeImageData, image.d:27-30 */
 
 /* lifetime: a new image is Image.init = errored with "Uninitialized image" (image.d:1609-1613) */
