@@ -168,13 +168,23 @@ extern(C)
                                             ubyte* out_, long* out_len, int* status_host, void* stream);
     void* gamut_hip_bmp_write_to_mem(const(void)* data, int pitch, int w, int h, int comp, int ppm_x, int ppm_y, int* out_len);
 
-    // GIF: GIFDecoder + loadGIF on the GPU, every frame composited into a layer (codecs/gif.d, plugins/gif.d:57-103); decode only
+    // GIF: GIFDecoder + loadGIF on the GPU, every frame composited into a layer (codecs/gif.d, plugins/gif.d:57-103)
     struct gamut_hip_gif_info { int width, height, layers, is_gif89; float pixel_aspect_ratio, fps; }
     int   gamut_hip_gif_read_header(const(ubyte)* data, size_t len, gamut_hip_gif_info* info);
     int   gamut_hip_gif_decode_batch_device(const(ubyte*)* data, const(size_t)* len, int count, const(long)* out_offset,
                                             const(long)* out_capacity, ubyte* out_, gamut_hip_gif_info* info, int* status_host, void* stream);
     float gamut_hip_gif_last_decode_kernel_ms();
     float gamut_hip_gif_last_kernel_ms(int which);
+    // GIF encode: saveGIF over msf_gif (plugins/gif.d:105-147, codecs/msf_gif.d), every layer a frame, byte for byte
+    long  gamut_hip_gif_encode_bound(int width, int height, int frames);
+    int   gamut_hip_gif_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(long)* src_layer_offset,
+                                            const(int)* width, const(int)* height, const(int)* frames,
+                                            const(int)* centiseconds, const(int)* max_bit_depth, const(int)* alpha_threshold,
+                                            int count, const(long)* out_offset, ubyte* out_, long* out_len, int* status_host,
+                                            void* stream);
+    void* gamut_hip_gif_write_to_mem(const(void)* data, int pitch, long layer_offset, int w, int h, int frames, int centiseconds,
+                                     int max_bit_depth, int alpha_threshold, int* out_len);
+    float gamut_hip_gif_last_encode_kernel_ms(int which);
 
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }

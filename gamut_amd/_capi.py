@@ -121,6 +121,11 @@ SIGNATURES = {
     "gamut_hip_gif_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, C.POINTER(_i64), C.POINTER(_i64), _vp, C.POINTER(GifInfo), _pi, _vp]),
     "gamut_hip_gif_last_decode_kernel_ms": (_f, []),
     "gamut_hip_gif_last_kernel_ms": (_f, [_i]),
+    "gamut_hip_gif_encode_bound": (_i64, [_i, _i, _i]),
+    "gamut_hip_gif_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), _pi, _pi, _pi, _pi, _pi, _pi, _i, C.POINTER(_i64), _vp,
+                                           C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_gif_write_to_mem": (_vp, [_vp, _i, _i64, _i, _i, _i, _i, _i, _i, _pi]),
+    "gamut_hip_gif_last_encode_kernel_ms": (_f, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

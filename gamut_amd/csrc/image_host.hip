@@ -840,6 +840,36 @@ static uint8_t* save_bmp(gamut_image* img, size_t* len)
     return r;
 }
 
+// saveGIF (plugins/gif.d:105-147): rgba8 only, every layer a frame of 7 centiseconds, maxBitDepth 16, alpha threshold 10
+static uint8_t* save_gif(gamut_image* img, size_t* len)
+{
+    const int w = img->_width, h = img->_height, frames = img->_layerCount;
+    if (img->_type != GAMUT_PIXEL_rgba8 || frames < 1) return nullptr;
+    const int64_t bound = gamut_hip_gif_encode_bound(w, h, frames);
+    if (bound == 0) return nullptr;
+    if (!img->_device) {
+        int n = 0;
+        uint8_t* r = (uint8_t*)gamut_hip_gif_write_to_mem(img->_data, (int)img->_pitch, (int64_t)img->_layerOffset, w, h, frames, 7, 16, 10, &n);
+        if (r) *len = (size_t)n;
+        return r;
+    }
+    hipStream_t st = thread_stream();
+    static thread_local PerDevice<DeviceScratch> out_pd;
+    uint8_t* d = nullptr;
+    try { d = (uint8_t*)out_pd.cur().get((size_t)bound, st); } catch (...) { d = nullptr; }
+    if (!d) return nullptr;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, layer = img->_layerOffset, off = 0; int64_t n = 0; int status = 0;
+    const int32_t W = w, H = h, F = frames;
+    if (gamut_hip_gif_encode_batch_device(&src, &pitch, &layer, &W, &H, &F, nullptr, nullptr, nullptr, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
+    uint8_t* r = (uint8_t*)malloc((size_t)n);
+    if (!r) return nullptr;
+    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); free(r); return nullptr;
+    }
+    *len = (size_t)n;
+    return r;
+}
+
 uint8_t* gamut_image_save_bmp_to_memory(gamut_image* img, int flags, size_t* len)
 {
     (void)flags;                                               // saveBMP ignores them
@@ -862,11 +892,12 @@ int gamut_image_save_bmp_to_file(gamut_image* img, const char* path, int flags)
 
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980
 {
-    (void)flags;                                               // saveQOI and saveJPEG ignore them
+    (void)flags;                                               // saveQOI, saveJPEG and saveGIF ignore them
     if (len) *len = 0;
     if (!img || !len || !img->isValid() || !img->_data) return nullptr;
     if (fif == GAMUT_FORMAT_QOI) return save_qoi(img, len);
     if (fif == GAMUT_FORMAT_JPEG) return save_jpeg(img, len);
+    if (fif == GAMUT_FORMAT_GIF) return save_gif(img, len);
     return nullptr;
 }
 int gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags)      // image.d:953-958

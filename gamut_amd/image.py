@@ -53,7 +53,7 @@ TO_GREYSCALE, TO_RGB, TO_ADD_ALPHA, TO_DROP_ALPHA, TO_PREMUL, TO_NO_PREMUL, TO_8
 LOAD_GREYSCALE, LOAD_ALPHA, LOAD_NO_ALPHA, LOAD_RGB = 0x10000, 0x20000, 0x40000, 0x80000
 LOAD_8BIT, LOAD_16BIT, LOAD_FP32, LOAD_PREMUL, LOAD_NO_PREMUL = 0x100000, 0x200000, 0x400000, 0x1000000, 0x2000000
 FORMAT_UNKNOWN, FORMAT_JPEG, FORMAT_PNG, FORMAT_QOI = -1, 0, 1, 2
-FORMAT_GIF = 6                                                 # ImageFormat.GIF: read only, every frame a layer
+FORMAT_GIF = 6                                                 # ImageFormat.GIF: every frame a layer, read and written (rgba8)
 FORMAT_BMP = 7                                                 # ImageFormat.BMP (types.d:14-28)
 ENCODE_PNG_COMPRESSION_DEFAULT, ENCODE_PNG_COMPRESSION_FAST, ENCODE_PNG_COMPRESSION_SMALL = 0, 2, 10                # types.d:220-248
 (ENCODE_PNG_COMPRESSION_0, ENCODE_PNG_COMPRESSION_1, ENCODE_PNG_COMPRESSION_2, ENCODE_PNG_COMPRESSION_3, ENCODE_PNG_COMPRESSION_4,
@@ -167,7 +167,7 @@ class Image:
     def scanptr(self, y): return self.L.gamut_image_scanptr(self.h, y)
     def layerptr(self, layer, y): return self.L.gamut_image_layerptr(self.h, layer, y)
 
-    # saving (image.d:940-1011): QOI and JPEG, layer 0, encoded on the GPU
+    # saving (image.d:940-1011): QOI and JPEG (layer 0) and GIF (rgba8, every layer a frame), encoded on the GPU
     def save_to_memory(self, fif, flags=0):
         """the encoded file as bytes, or None when the image cannot be saved in `fif`"""
         n = _sz(0)

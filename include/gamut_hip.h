@@ -458,7 +458,7 @@ int     gamut_hip_bmp_encode_batch_device(const uint8_t* const* src, const int64
 void*   gamut_hip_bmp_write_to_mem(const void* data, int pitch, int w, int h, int comp, int ppm_x, int ppm_y, int* out_len);
 
 /* ---- GIF (GIFDecoder, codecs/gif.d; loadGIF, plugins/gif.d:57-103) --------------------------------------------------------------
- * Decode only.  Every frame of the file, composited as the reference composites it (its disposal rules, its persistent GCE state --
+ * Decode: every frame of the file, composited as the reference composites it (its disposal rules, its persistent GCE state --
  * also from the counting pass of `open` into the decoding pass --, its pixel stepping for interlaced, overhanging and zero-sized
  * frames, its LZW verdicts), as `layers` tight rgba8 images of width x height.
  * Deliberate deviations (in each the reference reads or writes memory it does not own): both palette buffers start zeroed, so an
@@ -494,6 +494,44 @@ int gamut_hip_gif_decode_batch_device(const uint8_t* const* data, const size_t* 
  * records them apart; a measurement aid like the entry above, not part of the decode interface. */
 float gamut_hip_gif_last_decode_kernel_ms(void);
 float gamut_hip_gif_last_kernel_ms(int which);
+/* Encode: byte for byte what saveGIF (plugins/gif.d:105-147) gets from msf_gif (codecs/msf_gif.d: begin, one msf_gif_frame per layer,
+ * end) for a stack of rgba8 frames: the 32-byte header with the NETSCAPE2.0 loop block, per frame a GCE + image descriptor, a local
+ * colour table of 1 << tableBits entries and the LZW stream in 255-byte sub-blocks, then 0x3B.  Reproduced: the ordered dither and
+ * per-depth bit split of msf_cook_frame (vector body and scalar tail give the same values), the depth chain from frame to frame
+ * (start at min(max_bit_depth, previous depth + 160 / max(1, previous count)), down while >= 256 colours are used), the palette in
+ * ascending cooked value with bit replication, "unchanged pixel -> index 0" between frames of one bit split, disposal 0x09 in the
+ * block in front of a frame with transparent pixels, the greedy LZW parse with its reset at 4096 entries and its capped final widths.
+ * max_bit_depth is clamped to 1..16 as the reference clamps it; the delay keeps its low 16 bits.  saveGIF itself passes 7
+ * centiseconds, depth 16 and the alpha threshold 10.
+ * Deliberate deviations: a width or height below 1 or above 65535 (the reference writes truncated 16-bit fields), frames < 1, and a
+ * shape with width * height * 4 > INT_MAX (the reference's int sizes wrap) are refused.
+ * gamut_hip_gif_encode_bound: the reference's own reservation, 32 + frames * (32 + 768 + width * height * 3 / 2 + 256) + 1, which no
+ * file exceeds; 0 when the shape is refused. */
+int64_t gamut_hip_gif_encode_bound(int width, int height, int frames);
+/* batch: animation i has frames[i] rgba8 layers in DEVICE memory, layer l at src[i] + l * src_layer_offset[i], rows src_pitch[i]
+ * apart (negative allowed, any alignment), and is written to out + out_offset[i] (device, any alignment), which must have
+ * gamut_hip_gif_encode_bound(...) bytes; nothing outside [out_offset[i], out_offset[i] + out_len[i]) is written.  centiseconds,
+ * max_bit_depth, alpha_threshold: per animation, each array may be NULL (7, 16, 10).  out_len[i] / status_host[i] (host arrays;
+ * status_host may be NULL): a refused animation (or a NULL src[i], a negative out_offset[i]) gets GAMUT_HIP_ERR_INVALID_ARG and
+ * out_len 0, the others are still encoded, and the call returns the status of the lowest-numbered refused one.  Five launches and one
+ * wait per call whatever the frame counts (the frame-to-frame depth chain is walked on the device).  Returns when the encode has
+ * finished.  Working memory: the calling thread keeps, per device and for its lifetime like the library's other staging buffers
+ * (grown on demand, never shrunk), the largest scratch a call of its has needed -- one block slot of 32 + 768 + width * height * 3 / 2
+ * + 256 bytes and 16.4 KB of census bitmaps per frame of the batch (0.8 GB for 256 animations x 16 frames of 480 x 270);
+ * gamut_hip_gif_write_to_mem and the Image layer's GIF save keep a staging buffer of pixels + bound bytes each in the same way. */
+int     gamut_hip_gif_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const int64_t* src_layer_offset,
+                                          const int32_t* width, const int32_t* height, const int32_t* frames,
+                                          const int32_t* centiseconds, const int32_t* max_bit_depth, const int32_t* alpha_threshold,
+                                          int count, const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host,
+                                          void* stream);
+/* host pixels (layer l at data + l * layer_offset, rows `pitch` bytes apart, negative allowed) through pinned staging -> malloc'd
+ * file of *out_len bytes, or NULL on refusal (see last_error) */
+void*   gamut_hip_gif_write_to_mem(const void* data, int pitch, int64_t layer_offset, int w, int h, int frames, int centiseconds,
+                                   int max_bit_depth, int alpha_threshold, int* out_len);
+/* measurements: with GAMUT_HIP_GIF_TIMING=1 the encode call brackets each of its kernels with events; this returns the GPU
+ * milliseconds of kernel `which` of the calling thread's last encode call -- 0: colour census, 1: depth plan, 2: LZW, 3: block
+ * offsets, 4: gather --, -1 when timing is off, nothing was encoded or `which` is out of range */
+float gamut_hip_gif_last_encode_kernel_ms(int which);
 
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
