@@ -52,6 +52,11 @@ class GifInfo(C.Structure):                                    # gamut_hip_gif_i
                 ("pixel_aspect_ratio", C.c_float), ("fps", C.c_float)]
 
 
+class TgaInfo(C.Structure):                                    # gamut_hip_tga_info
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "bpp", "image_type", "rle", "indexed", "rgb16", "channels_in_file", "bottom_up",
+                                         "palette_start", "palette_len", "cmap_size", "data_offset", "detected")]
+
+
 class ImageInfo(C.Structure):                                  # gamut_hip_image_info
     _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels_in_file", C.c_int32), ("channels", C.c_int32)]
 
@@ -126,6 +131,10 @@ SIGNATURES = {
                                            C.POINTER(_i64), _pi, _vp]),
     "gamut_hip_gif_write_to_mem": (_vp, [_vp, _i, _i64, _i, _i, _i, _i, _i, _i, _pi]),
     "gamut_hip_gif_last_encode_kernel_ms": (_f, [_i]),
+    "gamut_hip_tga_read_header": (_i, [_vp, _sz, C.POINTER(TgaInfo)]),
+    "gamut_hip_tga_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _i, C.POINTER(_i64), _vp, C.POINTER(TgaInfo), _pi, _vp]),
+    "gamut_hip_tga_rle_window": (_i, []),
+    "gamut_hip_tga_last_decode_kernel_ms": (_f, []),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

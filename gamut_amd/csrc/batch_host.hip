@@ -14,6 +14,7 @@
 #include <mutex>
 
 namespace gamut {
+int tga_parse_header(const uint8_t* data, size_t len, gamut_hip_tga_info* info);                   // tga_host.hip
 namespace {
 
 // One persistent helper thread per format pipeline.  Jobs are handed over one at a time; the thread never exits (its thread-local
@@ -76,6 +77,11 @@ extern "C" int gamut_hip_identify_format(const uint8_t* b, size_t len)
         const uint32_t ds = (uint32_t)b[14] | (uint32_t)b[15] << 8 | (uint32_t)b[16] << 16 | (uint32_t)b[17] << 24;
         if (ds == 12 || ds == 40 || ds == 52 || ds == 56 || ds == 108 || ds == 124) return GAMUT_HIP_FORMAT_BMP;
     }
+    {                                                                                       // detectTGA plugins/tga.d:97-126: no signature, so LAST (image.d:1056)
+        gamut_hip_tga_info ti;
+        (void)tga_parse_header(b, b ? len : 0, &ti);
+        if (ti.detected) return GAMUT_HIP_FORMAT_TGA;
+    }
     return GAMUT_HIP_FORMAT_UNKNOWN;
 }
 
@@ -92,7 +98,7 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
     (void)hipGetDevice(&dev);
     try {
         // the files by format, in the caller's order
-        std::vector<int> idx[3], bmp_idx;
+        std::vector<int> idx[3], bmp_idx, tga_idx;
         std::vector<int> own_status;
         int* hst = status_host;
         if (!hst) { own_status.assign((size_t)count, GAMUT_HIP_OK); hst = own_status.data(); }
@@ -102,6 +108,7 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
             info[i].format = f;
             hst[i] = f < 0 ? GAMUT_HIP_ERR_UNSUPPORTED : GAMUT_HIP_OK;                       // kStrImageFormatUnidentified (image.d:1758-1762)
             if (f == GAMUT_HIP_FORMAT_BMP) bmp_idx.push_back(i);
+            else if (f == GAMUT_HIP_FORMAT_TGA) tga_idx.push_back(i);
             else if (f >= 0) idx[f].push_back(i);
         }
         struct Leg {
@@ -179,6 +186,30 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
                 snprintf(bres.msg, sizeof(bres.msg), "%s", m);
             }
         };
+        // The TGA files, if any: a fifth leg of the same kind (two launches), behind the BMP leg on the same thread and stream slot.
+        LegResult tres;
+        std::vector<gamut_hip_tga_info> ti(tga_idx.size()); std::vector<int> tst(tga_idx.size(), GAMUT_HIP_OK);
+        auto run_tga = [&](bool own_stream) {
+            if (tga_idx.empty()) return;
+            const size_t n = tga_idx.size();
+            std::vector<const uint8_t*> tptr(n); std::vector<size_t> tlen(n); std::vector<int64_t> toff(n);
+            for (size_t k = 0; k < n; ++k) { const int i = tga_idx[k]; tptr[k] = data[i]; tlen[k] = len[i]; toff[k] = out_offset[i]; }
+            hipStream_t ls = st;
+            if (own_stream) {
+                static thread_local PerDevice<hipStream_t> tga_stream_pd;
+                hipStream_t& s = tga_stream_pd.cur();
+                if ((!s && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) || hipStreamWaitEvent(s, fork, 0) != hipSuccess) {
+                    tres.rc = GAMUT_HIP_ERR_HIP; snprintf(tres.msg, sizeof(tres.msg), "decode_batch_device: stream setup of the TGA leg failed"); return;
+                }
+                ls = s;
+            }
+            tres.rc = gamut_hip_tga_decode_batch_device(tptr.data(), tlen.data(), (int)n, req_comps, toff.data(), out, ti.data(), tst.data(), ls);
+            if (tres.rc != GAMUT_HIP_OK) {
+                const char* m = gamut_hip_last_error();
+                if (!strncmp(m, "image ", 6) && strstr(m, ": ")) m = strstr(m, ": ") + 2;
+                snprintf(tres.msg, sizeof(tres.msg), "%s", m);
+            }
+        };
         // The longest legs first on the workers (PNG: inflate-bound, QOI: PCIe-bound), JPEG on the calling thread.  When another
         // thread's mixed batch holds the workers, the legs run one after the other here: same results.
         static const bool serial = [] { const char* e = getenv("GAMUT_HIP_MIXED_SERIAL"); return e && *e && atoi(e) != 0; }();     // measurements
@@ -199,9 +230,12 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
             run_leg(GAMUT_HIP_FORMAT_JPEG, true);
             try { run_bmp(true); }                                                            // (the workers still use this frame: nothing may leave it before `jobs` has waited)
             catch (...) { bres.rc = GAMUT_HIP_ERR_OUT_OF_MEMORY; snprintf(bres.msg, sizeof(bres.msg), "decode_batch_device: out of host memory in the BMP leg"); }
+            try { run_tga(true); }
+            catch (...) { tres.rc = GAMUT_HIP_ERR_OUT_OF_MEMORY; snprintf(tres.msg, sizeof(tres.msg), "decode_batch_device: out of host memory in the TGA leg"); }
         } else {
             for (int f = 0; f < 3; ++f) run_leg(f, false);
             run_bmp(false);
+            run_tga(false);
         }
         (void)hipSetDevice(dev);
 
@@ -226,7 +260,13 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
             info[i].width = bi[k].width; info[i].height = bi[k].height; info[i].channels_in_file = bi[k].channels_in_file; info[i].channels = req_comps;
             hst[i] = bst[k];
         }
+        for (size_t k = 0; k < tga_idx.size(); ++k) {
+            const int i = tga_idx[k];
+            info[i].width = ti[k].width; info[i].height = ti[k].height; info[i].channels_in_file = ti[k].channels_in_file; info[i].channels = req_comps;
+            hst[i] = tst[k];
+        }
         // a failure that is not a per-file verdict (allocation, HIP) is the call's; otherwise the lowest-numbered failing file's
+        if (tres.rc != GAMUT_HIP_OK && tres.rc != GAMUT_HIP_ERR_DECODE && tres.rc != GAMUT_HIP_ERR_INVALID_ARG) return set_error(tres.rc, "%s", tres.msg);
         if (bres.rc != GAMUT_HIP_OK && bres.rc != GAMUT_HIP_ERR_DECODE && bres.rc != GAMUT_HIP_ERR_INVALID_ARG) return set_error(bres.rc, "%s", bres.msg);
         for (int f = 0; f < 3; ++f)
             if (res[f].rc != GAMUT_HIP_OK && res[f].rc != GAMUT_HIP_ERR_DECODE && res[f].rc != GAMUT_HIP_ERR_UNSUPPORTED && res[f].rc != GAMUT_HIP_ERR_INVALID_ARG)
@@ -234,8 +274,9 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
         for (int i = 0; i < count; ++i) {
             if (hst[i] == GAMUT_HIP_OK) continue;
             const int f = info[i].format;
-            if (f < 0) return set_error(GAMUT_HIP_ERR_UNSUPPORTED, "image %d: format not identified (JPEG, PNG, QOI and BMP files are decoded)", i);
+            if (f < 0) return set_error(GAMUT_HIP_ERR_UNSUPPORTED, "image %d: format not identified (JPEG, PNG, QOI, BMP and TGA files are decoded)", i);
             if (f == GAMUT_HIP_FORMAT_BMP) return set_error(hst[i], "image %d: %s", i, bres.msg[0] ? bres.msg : "decoding failed");
+            if (f == GAMUT_HIP_FORMAT_TGA) return set_error(hst[i], "image %d: %s", i, tres.msg[0] ? tres.msg : "decoding failed");
             return set_error(hst[i], "image %d: %s", i, res[f].msg[0] ? res[f].msg : "decoding failed");
         }
         return GAMUT_HIP_OK;

@@ -444,6 +444,33 @@ struct gamut_image {
               info.pixels_per_meter_y == -1 ? -1.0f : info.pixels_per_meter_y / 39.37007874f);          // :134-135, convertInchesToMeters
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);
     }
+    void loadTGA(const uint8_t* bytes, size_t len, int flags)                               // plugins/tga.d:42-95
+    {
+        gamut_hip_tga_info hd, info;
+        const int hrc = gamut_hip_tga_read_header(bytes, len, &hd);
+        if (!hd.detected) { error(kStrImageDecodingFailed); return; }                       // getImageInfo :51-55
+        if (!imageIsValidSize(1, hd.width, hd.height)) { error(kStrImageTooLarge); return; } // :57-61
+        if (hrc != GAMUT_HIP_OK) { error(kStrImageDecodingFailed); return; }                // decodeImage's header part :63-71
+        const int comps = hd.channels_in_file;                                              // the file's own type; the flags act in convertTo
+        const size_t nbytes = (size_t)hd.width * hd.height * comps;
+        // the decode is the GPU's either way; a host image gets the pixels copied back from a staging allocation
+        uint8_t* dev = dmalloc(nbytes);
+        const int64_t zero = 0; int st = 0;
+        if (!dev || gamut_hip_tga_decode_batch_device(&bytes, &len, 1, 0, &zero, dev, &info, &st, nullptr) != GAMUT_HIP_OK) {
+            if (dev) (void)hipFree(dev);
+            error(kStrImageDecodingFailed); return;
+        }
+        uint8_t* decoded = dev;
+        if (!_device) {
+            decoded = (uint8_t*)malloc(nbytes ? nbytes : 1);
+            const bool ok = decoded && gamut_hip_memcpy_d2h(decoded, dev, nbytes, nullptr) == GAMUT_HIP_OK && gamut_hip_stream_synchronize(nullptr) == GAMUT_HIP_OK;
+            (void)hipFree(dev);
+            if (!ok) { free(decoded); error(kStrImageDecodingFailed); return; }
+        }
+        static const int t8[5] = { -1, GAMUT_PIXEL_l8, GAMUT_PIXEL_la8, GAMUT_PIXEL_rgb8, GAMUT_PIXEL_rgba8 };
+        adopt(decoded, hd.width, hd.height, t8[comps], comps, -1.0f, -1.0f);                // :87-88 GAMUT_UNKNOWN_ASPECT_RATIO / _RESOLUTION
+        convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);                           // :94
+    }
     // Layers of tight top-down rgba8 rows (device memory) into the image's own storage, whatever pitch and layer offset its constraints gave it
     bool fillLayersFromDevice(const uint8_t* dev, size_t layerBytes, size_t rowBytes)
     {
@@ -489,6 +516,7 @@ static int identify(const uint8_t* b, size_t len)
     if (b && len >= 4 && !memcmp(b, "qoif", 4)) return GAMUT_FORMAT_QOI;                    // detectQOI plugins/qoi.d:144-148
     if (b && len >= 6 && (!memcmp(b, "GIF87a", 6) || !memcmp(b, "GIF89a", 6))) return GAMUT_FORMAT_GIF;   // detectGIF plugins/gif.d:42-53
     if (gamut_hip_identify_format(b, len) == GAMUT_HIP_FORMAT_BMP) return GAMUT_FORMAT_BMP;  // detectBMP plugins/bmp.d:45-82
+    if (gamut_hip_identify_format(b, len) == GAMUT_HIP_FORMAT_TGA) return GAMUT_FORMAT_TGA;  // detectTGA plugins/tga.d:97-126, last (image.d:1056)
     return GAMUT_FORMAT_unknown;
 }
 
@@ -539,6 +567,7 @@ int gamut_image_load_from_memory(gamut_image* img, const uint8_t* bytes, size_t 
     case GAMUT_FORMAT_QOI:  img->loadQOI(bytes, len, flags); break;
     case GAMUT_FORMAT_BMP:  img->loadBMP(bytes, len, flags); break;
     case GAMUT_FORMAT_GIF:  img->loadGIF(bytes, len, flags); break;
+    case GAMUT_FORMAT_TGA:  img->loadTGA(bytes, len, flags); break;
     default: img->error(kStrImageFormatUnidentified); break;
     }
     return img->isValid();

@@ -533,6 +533,49 @@ void*   gamut_hip_gif_write_to_mem(const void* data, int pitch, int64_t layer_of
  * offsets, 4: gather --, -1 when timing is off, nothing was encoded or `which` is out of range */
 float gamut_hip_gif_last_encode_kernel_ms(int which);
 
+/* ---- TGA (TGADecoder, codecs/tga.d:283-647; loadTGA / detectTGA, plugins/tga.d) -- decode only ------------------------------------
+ * Every pixel what TGADecoder.decodeImage gives, bit for bit: image types 1 / 2 / 3 and their run-length forms 9 / 10 / 11, 8 / 15 /
+ * 16 / 24 / 32 bits per pixel, colour maps of 8 / 15 / 16 / 24 / 32-bit entries under 8- or 16-bit indices, either row order.  Kept
+ * from the reference: the colour map is reached by skipping palette_start BYTES (not entries); 15 / 16-bit pixels and colour-map
+ * entries are (v * 255) / 31 per channel and are not R/B swapped; 16-bit grey is two raw bytes; a colour-map index >= palette_len
+ * reads entry 0; run-length packets may cross row ends and the last one may overrun width * height (the surplus is dropped); the
+ * descriptor's alpha bits and x-origin bit are ignored, and so is anything behind the pixels.  A read past the end of the file fails
+ * (memory stream, io.d); a skip to exactly the end succeeds.
+ * Deliberate deviation: width * height * components > 2^31 - 1 (components: the file's or, if larger, the requested ones) is refused;
+ * the reference's `int` pixel offsets wrap there.
+ * (Declared typedef-first: the layout of this struct is pinned by tests/c/tga_abi_layout.c and tests/test_tga_cpu.py.) */
+typedef struct gamut_hip_tga_info gamut_hip_tga_info;
+struct gamut_hip_tga_info {
+    int32_t width, height;
+    int32_t bpp;                    /* bits per pixel of the file: the index size when indexed */
+    int32_t image_type;             /* 1, 2 or 3: the file's type after the - 8 of the run-length forms */
+    int32_t rle, indexed, rgb16;    /* 0 / 1 each; rgb16: pixels (or colour-map entries) are 5-5-5 words */
+    int32_t channels_in_file;       /* 1..4: l8, la8, rgb8, rgba8 (stbi__tga_get_comp of the cmap size when indexed, else of bpp) */
+    int32_t bottom_up;              /* 1: the file's first row is the bottom one (descriptor bit 5 clear) */
+    int32_t palette_start, palette_len, cmap_size;   /* 0 when the file has no colour map */
+    int32_t data_offset;            /* 18 + ID length: where the colour map (after palette_start more bytes) or the pixels begin */
+    int32_t detected;               /* 1: getImageInfo accepts bytes 0..16 (detectTGA), whatever the load verdict is */
+};
+/* the header alone (host, no GPU needed).  Two verdicts: info->detected is detectTGA's (the first 17 bytes), the return value is
+ * the load's -- GAMUT_HIP_OK, or GAMUT_HIP_ERR_DECODE where getImageInfo or the header part of decodeImage refuse (descriptor byte
+ * or ID field missing, too large).  Fields are filled as far as the header was read. */
+int gamut_hip_tga_read_header(const uint8_t* data, size_t len, gamut_hip_tga_info* info);
+/* `count` TGA files in host memory -> tight top-down rows of width * comps bytes at out + out_offset[i] (device).  req_comp 0: the
+ * file's own components, decodeImage's bytes; 3 / 4: what convertTo(rgb8 / rgba8) makes of them (grey replicated, a missing alpha
+ * 255, alpha dropped); anything else is GAMUT_HIP_ERR_INVALID_ARG.  Two launches for the whole batch (one over the unpacked
+ * files, one over the run-length ones), whatever count, geometries and variants.  info[i] / status_host[i] (either may be NULL) per
+ * file; a refused file gets GAMUT_HIP_ERR_DECODE and does not disturb the others; returns the status of the lowest-numbered refused
+ * file.  Unpacked files and colour maps that the file is too short for are refused on the host and write nothing; a run-length stream
+ * that ends before width * height pixels is refused on the device and may leave anything inside that image's own width * height *
+ * comps bytes.  Nothing outside those bytes is written.  Returns when the pixels are in place. */
+int gamut_hip_tga_decode_batch_device(const uint8_t* const* data, const size_t* len, int count, int req_comp,
+                                      const int64_t* out_offset, uint8_t* out, gamut_hip_tga_info* info, int* status_host, void* stream);
+/* the run-length kernel walks the packet stream in windows of this many bytes, counted from the first packet byte */
+int   gamut_hip_tga_rle_window(void);
+/* measurements: with GAMUT_HIP_TGA_TIMING=1 the decode call brackets its kernels (not the upload) with events; this returns the GPU
+ * milliseconds of the calling thread's last decode call, -1 when timing is off or nothing was decoded */
+float gamut_hip_tga_last_decode_kernel_ms(void);
+
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
  * procedures, a signature test each: plugins/jpeg.d:106-110, png.d:165-169, qoi.d:143-147) picks g_plugins[fif].loadProc
@@ -546,8 +589,12 @@ float gamut_hip_gif_last_encode_kernel_ms(int which);
  * the pixels are in place; the status of the lowest-numbered failing file, GAMUT_HIP_OK if none.
  * BMP files (detectBMP, plugins/bmp.d:45-82: 'B', 'M' and a known header size at offset 14; tested after the three signatures above)
  * are a fourth, short leg: gamut_hip_bmp_decode_batch_device on a stream of its own, run from the calling thread once the workers have
- * their legs and before they are waited for. */
-enum { GAMUT_HIP_FORMAT_UNKNOWN = -1, GAMUT_HIP_FORMAT_JPEG = 0, GAMUT_HIP_FORMAT_PNG = 1, GAMUT_HIP_FORMAT_QOI = 2, GAMUT_HIP_FORMAT_BMP = 7 };
+ * their legs and before they are waited for.
+ * TGA files (detectTGA: gamut_hip_tga_read_header's `detected`; the format has no signature, so it is tested LAST, image.d:1056) are
+ * a fifth leg of the same kind, gamut_hip_tga_decode_batch_device, run behind the BMP leg.  A file that is detected and fails to load
+ * is that image's GAMUT_HIP_ERR_DECODE. */
+enum { GAMUT_HIP_FORMAT_UNKNOWN = -1, GAMUT_HIP_FORMAT_JPEG = 0, GAMUT_HIP_FORMAT_PNG = 1, GAMUT_HIP_FORMAT_QOI = 2, GAMUT_HIP_FORMAT_TGA = 5,
+       GAMUT_HIP_FORMAT_BMP = 7 };
 typedef struct gamut_hip_image_info { int32_t format, width, height, channels_in_file, channels; } gamut_hip_image_info;
 int gamut_hip_identify_format(const uint8_t* data, size_t len);
 int gamut_hip_decode_batch_device(const uint8_t* const* data, const size_t* len, int count, int req_comps,

@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ImageFormat (types.d:14-28) */
-enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_GIF = 6, GAMUT_FORMAT_BMP = 7 };   /* ImageFormat, types.d:14-21 */
+enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_TGA = 5, GAMUT_FORMAT_GIF = 6, GAMUT_FORMAT_BMP = 7 };   /* ImageFormat, types.d:14-21 */
 
 /* LoadFlags (types.d:139-197) */
 enum {
@@ -53,7 +53,7 @@ int  gamut_compute_requested_image_components(int flags);              /* intern
 int  gamut_valid_load_flags(int flags);                                /* internals/types.d:563-578 */
 int  gamut_layout_constraints_valid(int constraints);                  /* internals/types.d:267-289 */
 int  gamut_layout_constraints_compatible(int newer, int older);        /* internals/types.d:241-264 */
-int  gamut_identify_format_from_memory(const uint8_t* bytes, size_t len);   /* image.d:1038-1061 (JPEG, PNG, QOI, GIF, BMP) */
+int  gamut_identify_format_from_memory(const uint8_t* bytes, size_t len);   /* image.d:1038-1061 (JPEG, PNG, QOI, GIF, BMP; TGA, which has no signature, last) */
 void gamut_free_image_data(void* mallocArea);                          /* freeImageData, image.d:27-30 */
 
 /* lifetime: a new image is Image.init = errored with "Uninitialized image" (image.d:1609-1613) */
@@ -69,7 +69,9 @@ int gamut_image_create_with_no_data(gamut_image* img, int width, int height, int
 /* createView (image.d:697): borrow caller memory; pitch may be negative */
 int gamut_image_create_view(gamut_image* img, void* data, int width, int height, int type, int pitchInBytes);
 
-/* load (image.d:886-906): flags = LOAD_* | LAYOUT_*; returns isValid() */
+/* load (image.d:886-906): flags = LOAD_* | LAYOUT_*; returns isValid().  A TGA file (plugins/tga.d:42-95) loads as l8 / la8 / rgb8 /
+ * rgba8 by its header, aspect ratio and resolution unknown, then convertTo(applyLoadFlags(type, flags), layout); "Image decoding
+ * failed" where the header, the colour map or the pixel stream is refused (gamut_hip_tga_*). */
 int gamut_image_load_from_memory(gamut_image* img, const uint8_t* bytes, size_t len, int flags);
 
 /* conversion (image.d:1082-1332): all forward to convertTo */
