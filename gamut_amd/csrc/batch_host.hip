@@ -92,9 +92,8 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
     if (count < 0 || (req_comps != 3 && req_comps != 4) || (count > 0 && (!data || !len || !out_offset || !out || !info)))
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "decode_batch_device: bad arguments (req_comps is 3 or 4: what all three decoders produce)");
     if (count == 0) return GAMUT_HIP_OK;
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
+    int dev = 0;
     (void)hipGetDevice(&dev);
     try {
         // the files by format, in the caller's order

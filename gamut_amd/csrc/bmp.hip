@@ -20,7 +20,8 @@
 // it in LDS from aligned dword loads of the source (any pitch, any alignment; v_alignbyte_b32 / v_perm_b32) and stores them as aligned
 // 16-byte chunks, head and tail by bytes.  Decode stores its units' bytes the same way (flush_run).  DEVIATION: the 0..3 pad bytes
 // of a 24-bit row, which the reference writes from an uninitialised malloc buffer, are zero.
-#include "common.hpp"
+#include "encode_host.hpp"
+#include "device_util.hpp"
 
 namespace gamut {
 int bmp_parse_header(const uint8_t* data, size_t len, int req_comp, gamut_hip_bmp_info* info);     // bmp_host.hip
@@ -43,22 +44,6 @@ struct DecImg {
     uint32_t word;                                                           // the image's alpha-OR word
 };
 
-template <class Img> __device__ __forceinline__ int find_image(const Img* imgs, int n, uint32_t u)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (imgs[mid].unit0 <= u) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t file_dword(const DecImg& im, uint64_t pos)           // pos - pix_off is a multiple of 4
-{
-    return pos < im.avail ? *reinterpret_cast<const uint32_t*>(im.file + pos) : 0u;
-}
-__device__ __forceinline__ uint32_t file_byte(const DecImg& im, uint64_t pos) { return pos < im.avail ? im.file[pos] : 0u; }
-
-__device__ __forceinline__ uint32_t byte_of(const uint32_t* v, int k) { return (v[k >> 2] >> (8 * (k & 3))) & 255u; }
-__device__ __forceinline__ void set_byte(uint32_t* v, int k, uint32_t b) { v[k >> 2] |= b << (8 * (k & 3)); }
-
 // stbi__shiftsigned(v & mask, shift, bits) :2493-2511
 __device__ __forceinline__ uint32_t channel(const DecImg& im, uint32_t v, int c)
 {
@@ -69,24 +54,6 @@ __device__ __forceinline__ uint32_t channel(const DecImg& im, uint32_t v, int c)
     return (x * im.mul[c]) >> im.down[c];
 }
 
-// A run of n bytes that a workgroup has assembled in LDS (S, dword array, one spare dword behind the run) goes to dst, which may have
-// any alignment: the head up to the first 16-byte boundary and the tail by bytes, the body as aligned 16-byte stores whose dwords are
-// taken from the LDS dwords at the matching offset with v_alignbyte_b32 (the discipline of convert.hip's staged stores).
-__device__ __forceinline__ void flush_run(const uint32_t* S, uint8_t* dst, uint32_t n, uint32_t tid)
-{
-    const uint32_t head = min(n, (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u));
-    if (tid < head) dst[tid] = (uint8_t)byte_of(S, (int)tid);
-    const uint32_t chunks = (n - head) >> 4;
-    for (uint32_t c = tid; c < chunks; c += kThreads) {
-        const uint32_t r = head + 16u * c, i = r >> 2, sh = r & 3u;
-        const uint32_t a0 = S[i], a1 = S[i + 1], a2 = S[i + 2], a3 = S[i + 3], a4 = S[i + 4];
-        *reinterpret_cast<uint4*>(dst + r) = make_uint4(__builtin_amdgcn_alignbyte(a1, a0, sh), __builtin_amdgcn_alignbyte(a2, a1, sh),
-                                                        __builtin_amdgcn_alignbyte(a3, a2, sh), __builtin_amdgcn_alignbyte(a4, a3, sh));
-    }
-    const uint32_t t = head + 16u * chunks + tid;
-    if (t < n) dst[t] = (uint8_t)byte_of(S, (int)t);
-}
-
 __device__ __forceinline__ uint32_t luma(uint32_t px) { return ((px & 255u) * 77u + (px >> 8 & 255u) * 150u + (px >> 16 & 255u) * 29u) >> 8; }   // stbi__compute_y
 
 __global__ __launch_bounds__(kThreads) void k_bmp_decode(const DecImg* imgs, int n_img, uint8_t* out, uint32_t* alpha_or)
@@ -94,7 +61,7 @@ __global__ __launch_bounds__(kThreads) void k_bmp_decode(const DecImg* imgs, int
     __shared__ uint32_t pal[256];
     __shared__ uint32_t run[kThreads * 8 + 4];                               // the unit's output bytes: 256 lanes x up to 32
     const uint32_t u = blockIdx.x;
-    const DecImg im = imgs[find_image(imgs, n_img, u)];
+    const DecImg im = imgs[find_unit<&DecImg::unit0>(imgs, n_img, u)];
     const uint32_t lu = u - im.unit0, j = lu / im.segs, seg = lu - j * im.segs;
     const uint32_t tid = threadIdx.x;
     if (im.bpp <= 8) {                                                       // (uniform over the workgroup)
@@ -157,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void k_bmp_decode(const DecImg* imgs, int
     {
         const uint64_t xs = (uint64_t)seg * kThreads * ppl;                  // the unit's first pixel; (uniform over the workgroup)
         const uint32_t y = im.top_down ? j : im.h - 1 - j;                   // the reference flips bottom-up files :2445-2454
-        flush_run(run, out + im.out_off + ((uint64_t)y * im.w + xs) * im.comps, (uint32_t)min((uint64_t)kThreads * ppl, im.w - xs) * im.comps, tid);
+        flush_run<kThreads>(run, out + im.out_off + ((uint64_t)y * im.w + xs) * im.comps, (uint32_t)min((uint64_t)kThreads * ppl, im.w - xs) * im.comps, tid);
     }
     if (im.cand) {                                                           // (uniform over the workgroup: every lane takes part)
         #pragma unroll
@@ -179,20 +146,9 @@ __global__ __launch_bounds__(kThreads) void k_bmp_alpha(const DecImg* imgs, cons
 int high_bit(uint32_t z) { int n = -1; while (z) { ++n; z >>= 1; } return n; }            // stbi__high_bit :2468
 int bitcount(uint32_t a) { int n = 0; while (a) { n += a & 1u; a >>= 1; } return n; }     // stbi__bitcount :2480
 
-bool have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return false; }
-    return true;
-}
-
 // Measurements (tools/bmp_bench.py): with GAMUT_HIP_BMP_TIMING=1 the decode call brackets its kernels -- not the upload -- with events
 // and keeps the GPU time of the calling thread's last call; the blob is resident in HBM when the first event is reached.
 thread_local float t_last_decode_kernel_ms = -1.0f;
-bool timing_on() { static const bool on = [] { const char* e = getenv("GAMUT_HIP_BMP_TIMING"); return e && *e && atoi(e) != 0; }(); return on; }
-
-size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int decode_batch(const uint8_t* const* data, const size_t* len, int count, int req_comp, const int64_t* out_offset, uint8_t* out,
                  gamut_hip_bmp_info* info, int* status_host, hipStream_t stream)
@@ -268,20 +224,17 @@ int decode_batch(const uint8_t* const* data, const size_t* len, int count, int r
         if (!cand.empty()) memcpy(h + o_cand, cand.data(), cand.size() * 4);
         GAMUT_HIP_CHECK(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, stream));
         const DecImg* dimg = (const DecImg*)(d + o_img);
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (timing_on() && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess || hipEventRecord(ev0, stream) != hipSuccess)) {
-            (void)hipGetLastError(); ev0 = nullptr;
-        }
+        static const bool timing = env_flag("GAMUT_HIP_BMP_TIMING");
+        KernelTimer<2> timer(timing);
+        timer.mark(stream);
         hipLaunchKernelGGL(k_bmp_decode, dim3((uint32_t)units), dim3(kThreads), 0, stream, dimg, n, out, (uint32_t*)(d + o_word));
         for (size_t c0 = 0; c0 < cand.size(); c0 += 65535)                 // (grid.y holds 65535)
             hipLaunchKernelGGL(k_bmp_alpha, dim3(64, (uint32_t)std::min<size_t>(65535, cand.size() - c0)), dim3(kThreads), 0, stream, dimg,
                                (const int*)(d + o_cand) + c0, (const uint32_t*)(d + o_word), out);
         if (int rc = launch_status("bmp_decode")) return rc;
-        if (ev0) (void)hipEventRecord(ev1, stream);
+        timer.mark(stream);
         GAMUT_HIP_CHECK(hipStreamSynchronize(stream));
-        if (ev0) { if (hipEventElapsedTime(&t_last_decode_kernel_ms, ev0, ev1) != hipSuccess) { (void)hipGetLastError(); t_last_decode_kernel_ms = -1.0f; } }
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
+        timer.finish(&t_last_decode_kernel_ms);
     }
     if (first_bad >= 0) return set_error(first_rc, "image %d: %s", first_bad, first_msg);
     return GAMUT_HIP_OK;
@@ -317,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void k_bmp_encode(const EncImg* imgs, int
 {
     __shared__ uint32_t run[kEncRun / 4 + 4];
     const uint32_t u = blockIdx.x;
-    const EncImg im = imgs[find_image(imgs, n_img, u)];
+    const EncImg im = imgs[find_unit<&EncImg::unit0>(imgs, n_img, u)];
     const uint32_t lu = u - im.unit0, tid = threadIdx.x;
     uint8_t* file = out + im.out_off;
     if (lu == 0 && tid < (uint32_t)kFileHeader) file[tid] = headers[(size_t)im.hdr * 128 + tid];
@@ -344,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void k_bmp_encode(const EncImg* imgs, int
         run[d] = v;
     }
     __syncthreads();
-    flush_run(run, file + kFileHeader + b0, n, tid);
+    flush_run<kThreads>(run, file + kFileHeader + b0, n, tid);
 }
 
 int64_t encode_bound(int w, int h, int comp)                                  // plugins/bmp.d:174-189
@@ -466,32 +419,12 @@ void* gamut_hip_bmp_write_to_mem(const void* data, int pitch, int w, int h, int 
         set_error(GAMUT_HIP_ERR_INVALID_ARG, "bmp_write_to_mem: invalid arguments"); return nullptr;
     }
     if (!have_device()) return nullptr;
-    const size_t row = (size_t)w * comp, px_bytes = row * h, bound = (size_t)encode_bound(w, h, comp);
-    const size_t o_out = up256(px_bytes);
-    hipStream_t st = thread_stream();
-    uint8_t* d = nullptr; uint8_t* hp = nullptr;
-    try {
-        static thread_local PerDevice<DeviceScratch> dev_pd;
-        static thread_local PerDevice<PinnedScratch> pinned_pd;
-        d = (uint8_t*)dev_pd.cur().get(o_out + bound, st);
-        hp = pinned_pd.cur().get(px_bytes, st);
-    } catch (...) { d = nullptr; }
-    if (!d || !hp) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "bmp_write_to_mem: staging of %zu bytes failed", o_out + bound); return nullptr; }
-    for (int y = 0; y < h; ++y) memcpy(hp + row * y, (const uint8_t*)data + (ptrdiff_t)pitch * y, row);
-    if (hipMemcpyAsync(d, hp, px_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_HIP, "bmp_write_to_mem: upload failed"); return nullptr; }
-    const uint8_t* src = d; const int64_t spitch = (int64_t)row, off = (int64_t)o_out; int64_t n = 0; int status = 0;
     const int32_t W = w, H = h, Cc = comp, PX = ppm_x, PY = ppm_y;
-    int rc;
-    try { rc = encode_batch(&src, &spitch, &W, &H, &Cc, &PX, &PY, 1, &off, d, &n, &status, st); }
-    catch (...) { rc = set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "bmp_write_to_mem: out of host memory"); }
-    if (rc != GAMUT_HIP_OK) return nullptr;
-    uint8_t* result = (uint8_t*)malloc((size_t)n);
-    if (!result) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "bmp_write_to_mem: out of memory"); return nullptr; }
-    if (hipMemcpyAsync(result, d + o_out, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(result); set_error(GAMUT_HIP_ERR_HIP, "bmp_write_to_mem: copy back failed"); return nullptr;
-    }
-    *out_len = (int)n;
-    return result;
+    return encode_host_image("bmp_write_to_mem", HostRows{ data, pitch, (size_t)w * comp, h, 1, 0 }, (size_t)encode_bound(w, h, comp), out_len,
+        [&](const uint8_t* src, int64_t spitch, int64_t, int64_t off, uint8_t* d, int64_t* n, hipStream_t st) {
+            int status = 0;
+            return encode_batch(&src, &spitch, &W, &H, &Cc, &PX, &PY, 1, &off, d, n, &status, st);
+        });
 }
 
 } // extern "C"

@@ -28,6 +28,15 @@ hipStream_t thread_stream();
 // enqueued by a caller that never touches streams is ordered with everything else it does
 inline hipStream_t pick_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Is there a HIP device?  If not, the thread's message says so (GAMUT_HIP_ERR_NO_DEVICE is what the caller returns, NULL from a
+// call that hands back a pointer) and HIP's own last error is cleared.  Every compute entry point asks this behind its argument
+// checks and before it touches an output: there is no CPU fallback.
+bool have_device();
+
+inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline bool env_flag(const char* name) { const char* e = getenv(name); return e && *e && atoi(e) != 0; }      // GAMUT_HIP_*_TIMING=1
+
 // A host process may drive several GPUs from one thread (hipSetDevice between calls) -- what a D host with "one host thread +
 // one HIP stream per GPU"  does as well as a thread that simply serves two devices in turn.  Everything the
 // library caches per thread -- staging buffers, private streams, events -- therefore lives in a slot of the CURRENT device:
@@ -124,6 +133,34 @@ struct PinnedScratch {                  // page-locked host memory: uploads from
         }
         last_user = stream;
         return p;
+    }
+};
+
+// Measurements: N marks on a call's stream, and the GPU milliseconds between consecutive marks for the codec's *_last_*_kernel_ms
+// getter.  `enabled` is the codec's GAMUT_HIP_*_TIMING flag, read once where the timer is used (static const bool ... = env_flag(...));
+// a timer that is not enabled does nothing at all.  The events are destroyed on every way out of the call.
+template <int N> struct KernelTimer {
+    hipEvent_t ev[N] = {}; int marks = 0; const bool enabled; bool ok;
+    explicit KernelTimer(bool on) : enabled(on), ok(on)
+    {
+        if (enabled) for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+    }
+    ~KernelTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    KernelTimer(const KernelTimer&) = delete;
+    KernelTimer& operator=(const KernelTimer&) = delete;
+    void mark(hipStream_t stream)
+    {
+        if (!ok) return;
+        if (marks == N || hipEventRecord(ev[marks], stream) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+        ++marks;
+    }
+    // once the stream has been waited for: ms_out[k] = time between marks k and k + 1, or -1 for all N - 1 when anything failed
+    void finish(float* ms_out)
+    {
+        if (!enabled) return;
+        if (marks != N) ok = false;
+        for (int k = 0; k + 1 < N; ++k)
+            if (!ok || hipEventElapsedTime(&ms_out[k], ev[k], ev[k + 1]) != hipSuccess) { (void)hipGetLastError(); ms_out[k] = -1.0f; }
     }
 };
 

@@ -86,9 +86,7 @@ extern "C" {
 int gamut_hip_flip_device(int type, void* data, int64_t pitch, int64_t layerOffset, int width, int height, int layers, int vertical, void* stream)
 {
     clear_error();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     return flip_device(type, data, pitch, layerOffset, width, height, layers, vertical, pick_stream(stream));
 }
 
@@ -96,9 +94,7 @@ int gamut_hip_flip_device(int type, void* data, int64_t pitch, int64_t layerOffs
 int gamut_hip_flip(int type, uint8_t* data, int pitch, int width, int height, int vertical)
 {
     clear_error();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     if (!valid_type(type) || width < 0 || height < 0) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "flip: bad arguments");
     if (width == 0 || height == 0) return GAMUT_HIP_OK;
     if (!data) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "flip: null pointer");

@@ -23,6 +23,7 @@
 // the row order and the frame's palette snapshot, and stores the pixel to that frame's layer: a wave stores 256 consecutive bytes.
 // Files with a refused frame are left untouched.
 #include "gif_host.hpp"
+#include "device_util.hpp"
 #include <string>
 
 namespace gamut {
@@ -122,19 +123,12 @@ k_gif_lzw(const DFrame* __restrict__ frames, const uint8_t* __restrict__ blob, u
     }
 }
 
-__device__ __forceinline__ int find_file(const DFile* files, int n, uint32_t u)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (files[mid].unit0 <= u) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 __global__ void __launch_bounds__(kComposeThreads)
 k_gif_compose(const DFile* __restrict__ files, int nfiles, const DFrame* __restrict__ frames, const uint8_t* __restrict__ idx_all,
               const uint32_t* __restrict__ frame_count, const uint32_t* __restrict__ file_bad, const uint32_t* __restrict__ palettes,
               const uint16_t* __restrict__ rowmaps, uint8_t* out)
 {
-    const int fi = find_file(files, nfiles, blockIdx.x);
+    const int fi = find_unit<&DFile::unit0>(files, nfiles, blockIdx.x);
     const DFile& f = files[fi];
     if (file_bad[fi]) return;
     const uint64_t npx = (uint64_t)f.w * f.h;
@@ -167,19 +161,9 @@ k_gif_compose(const DFile* __restrict__ files, int nfiles, const DFrame* __restr
     }
 }
 
-bool have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return false; }
-    return true;
-}
-
 // Measurements (tools/gif_bench.py): with GAMUT_HIP_GIF_TIMING=1 the decode call brackets each of its two kernels -- not the upload --
 // with events and keeps the GPU times of the calling thread's last call.
 thread_local float t_last_ms[2] = { -1.0f, -1.0f };
-bool timing_on() { static const bool on = [] { const char* e = getenv("GAMUT_HIP_GIF_TIMING"); return e && *e && atoi(e) != 0; }(); return on; }
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int decode_batch(const uint8_t* const* data, const size_t* len, int count, const int64_t* out_offset, const int64_t* out_capacity, uint8_t* out,
                  gamut_hip_gif_info* info, int* status_host, hipStream_t stream, bool& per_file)
@@ -259,28 +243,21 @@ int decode_batch(const uint8_t* const* data, const size_t* len, int count, const
         GAMUT_HIP_CHECK(hipMemcpyAsync(d, h, o_cnt, hipMemcpyHostToDevice, stream));
         const DFrame* dfr = (const DFrame*)(d + o_frames);
         uint32_t* dbad = (uint32_t*)(d + o_bad); uint32_t* dcnt = (uint32_t*)(d + o_cnt);
-        struct Events {                                               // destroyed on every way out of the call
-            hipEvent_t e[3] = { nullptr, nullptr, nullptr };
-            ~Events() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-        } events;
-        hipEvent_t* ev = events.e;
-        bool timed = timing_on();
-        if (timed) for (auto& e : events.e) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); timed = false; }
-        if (timed) (void)hipEventRecord(ev[0], stream);
+        static const bool timing = env_flag("GAMUT_HIP_GIF_TIMING");
+        KernelTimer<3> timer(timing);
+        timer.mark(stream);
         hipLaunchKernelGGL(k_gif_lzw, dim3((uint32_t)nfr), dim3(kWave), 0, stream, dfr, d + o_blob, didx, dcnt, dbad);
         if (int rc = launch_status("gif_lzw")) return rc;
-        if (timed) (void)hipEventRecord(ev[1], stream);
+        timer.mark(stream);
         if (units) {
             hipLaunchKernelGGL(k_gif_compose, dim3((uint32_t)units), dim3(kComposeThreads), 0, stream, (const DFile*)(d + o_files), nf, dfr, didx, dcnt,
                                dbad, (const uint32_t*)(d + o_pal), (const uint16_t*)(d + o_map), out);
             if (int rc = launch_status("gif_compose")) return rc;
         }
-        if (timed) (void)hipEventRecord(ev[2], stream);
+        timer.mark(stream);
         GAMUT_HIP_CHECK(hipMemcpyAsync(h + o_bad, dbad, (size_t)nf * 4, hipMemcpyDeviceToHost, stream));
         GAMUT_HIP_CHECK(hipStreamSynchronize(stream));
-        if (timed) {
-            for (int k = 0; k < 2; ++k) if (hipEventElapsedTime(&t_last_ms[k], ev[k], ev[k + 1]) != hipSuccess) { (void)hipGetLastError(); t_last_ms[k] = -1.0f; }
-        }
+        timer.finish(t_last_ms);
         bad_host.assign((const uint32_t*)(h + o_bad), (const uint32_t*)(h + o_bad) + nf);
         for (int k = 0; k < nf; ++k)
             if (bad_host[(size_t)k]) { rcs[(size_t)which[(size_t)k]] = GAMUT_HIP_ERR_DECODE; msgs[(size_t)which[(size_t)k]] = "gif: corrupt raster data"; }

@@ -376,25 +376,25 @@ k_gifenc_gather(const GifEncAnim* __restrict__ anims, const GifEncFrame* __restr
 
 int gifenc_launch(const GifEncAnim* anims, int n_anim, const GifEncFrame* frames, uint32_t n_frames, uint32_t census_units, uint32_t gather_units,
                   uint32_t* bitmaps, uint32_t* transp, GifEncPlan* plans, uint8_t* slots, int64_t* total_len, uint8_t* out, const GifEncMul& mul,
-                  hipStream_t stream, hipEvent_t* ev)
+                  hipStream_t stream, KernelTimer<6>& timer)
 {
-    if (ev) (void)hipEventRecord(ev[0], stream);
+    timer.mark(stream);
     hipLaunchKernelGGL(k_gifenc_census, dim3(census_units), dim3(kCensusThreads), 0, stream, anims, frames, n_frames, bitmaps, transp, mul);
     if (int rc = launch_status("gifenc_census")) return rc;
-    if (ev) (void)hipEventRecord(ev[1], stream);
+    timer.mark(stream);
     hipLaunchKernelGGL(k_gifenc_plan, dim3((uint32_t)n_anim), dim3(kWave), 0, stream, anims, (const uint32_t*)bitmaps, (const uint32_t*)transp, plans);
     if (int rc = launch_status("gifenc_plan")) return rc;
-    if (ev) (void)hipEventRecord(ev[2], stream);
+    timer.mark(stream);
     hipLaunchKernelGGL(k_gifenc_lzw, dim3(n_frames), dim3(kWave), 0, stream, anims, frames, (const uint32_t*)bitmaps, plans, slots, mul);
     if (int rc = launch_status("gifenc_lzw")) return rc;
-    if (ev) (void)hipEventRecord(ev[3], stream);
+    timer.mark(stream);
     hipLaunchKernelGGL(k_gifenc_offsets, dim3((uint32_t)n_anim), dim3(kWave), 0, stream, anims, plans, total_len);
     if (int rc = launch_status("gifenc_offsets")) return rc;
-    if (ev) (void)hipEventRecord(ev[4], stream);
+    timer.mark(stream);
     hipLaunchKernelGGL(k_gifenc_gather, dim3(gather_units), dim3(kGatherThreads), 0, stream, anims, frames, n_frames, (const GifEncPlan*)plans,
                        (const uint8_t*)slots, (const int64_t*)total_len, out);
     if (int rc = launch_status("gifenc_gather")) return rc;
-    if (ev) (void)hipEventRecord(ev[5], stream);
+    timer.mark(stream);
     return GAMUT_HIP_OK;
 }
 

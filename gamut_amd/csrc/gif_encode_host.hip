@@ -12,6 +12,7 @@
 //   * frames < 1 (saveGIF :116): refused, as there;
 //   * a shape with width * height * 4 > INT_MAX (the reference's int sizes, :337-346 and :530, wrap): refused.
 #include "gif_encode_host.hpp"
+#include "encode_host.hpp"
 
 namespace gamut {
 
@@ -36,19 +37,9 @@ GifEncMul gifenc_mul_table()
 
 namespace {
 
-bool have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return false; }
-    return true;
-}
-
 // Measurements (tools/gif_encode_bench.py): with GAMUT_HIP_GIF_TIMING=1 the encode call brackets each of its five kernels with events
 // and keeps the GPU times of the calling thread's last call: census, plan, LZW, offsets, gather.
 thread_local float t_last_ms[5] = { -1.0f, -1.0f, -1.0f, -1.0f, -1.0f };
-bool timing_on() { static const bool on = [] { const char* e = getenv("GAMUT_HIP_GIF_TIMING"); return e && *e && atoi(e) != 0; }(); return on; }
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const int64_t* src_layer_offset, const int32_t* width, const int32_t* height,
                  const int32_t* frames, const int32_t* centiseconds, const int32_t* max_bit_depth, const int32_t* alpha_threshold, int count,
@@ -100,21 +91,17 @@ int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const int6
         memcpy(h + o_fr, fr.data(), nfr * sizeof(GifEncFrame));
         GAMUT_HIP_CHECK(hipMemcpyAsync(d, h, o_up_end, hipMemcpyHostToDevice, stream));
         GAMUT_HIP_CHECK(hipMemsetAsync(d + o_tr, 0, total - o_tr, stream));
-        struct Events {                                               // destroyed on every way out of the call
-            hipEvent_t e[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-            ~Events() { for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-        } events;
-        bool timed = timing_on();
-        if (timed) for (auto& e : events.e) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); timed = false; }
+        static const bool timing = env_flag("GAMUT_HIP_GIF_TIMING");
+        KernelTimer<6> timer(timing);
         for (float& t : t_last_ms) t = -1.0f;
         int64_t* dlen = (int64_t*)(d + o_len);
         if (int rc = gifenc_launch((const GifEncAnim*)(d + o_anim), n, (const GifEncFrame*)(d + o_fr), (uint32_t)nfr, (uint32_t)census_units,
                                    (uint32_t)gather_units, (uint32_t*)(d + o_bm), (uint32_t*)(d + o_tr), (GifEncPlan*)(d + o_plan), dslots, dlen, out,
-                                   gifenc_mul_table(), stream, timed ? events.e : nullptr)) return rc;
+                                   gifenc_mul_table(), stream, timer)) return rc;
         int64_t* hlen = (int64_t*)(h + o_up_end);
         GAMUT_HIP_CHECK(hipMemcpyAsync(hlen, dlen, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
         GAMUT_HIP_CHECK(hipStreamSynchronize(stream));
-        if (timed) for (int k = 0; k < 5; ++k) if (hipEventElapsedTime(&t_last_ms[k], events.e[k], events.e[k + 1]) != hipSuccess) { (void)hipGetLastError(); t_last_ms[k] = -1.0f; }
+        timer.finish(t_last_ms);
         for (int k = 0; k < n; ++k) {
             const int i = which[(size_t)k];
             if (hlen[k] > 0) { out_len[i] = hlen[k]; continue; }
@@ -165,34 +152,12 @@ void* gamut_hip_gif_write_to_mem(const void* data, int pitch, int64_t layer_offs
         set_error(GAMUT_HIP_ERR_INVALID_ARG, "gif_write_to_mem: invalid arguments"); return nullptr;
     }
     if (!have_device()) return nullptr;
-    const size_t row = (size_t)w * 4, layer = row * h, px_bytes = layer * frames, bound = (size_t)bound64;
-    const size_t o_out = up256(px_bytes);
-    hipStream_t st = thread_stream();
-    uint8_t* d = nullptr; uint8_t* hp = nullptr;
-    try {
-        static thread_local PerDevice<DeviceScratch> dev_pd;
-        static thread_local PerDevice<PinnedScratch> pinned_pd;
-        d = (uint8_t*)dev_pd.cur().get(o_out + bound, st);
-        hp = pinned_pd.cur().get(px_bytes, st);
-    } catch (...) { d = nullptr; }
-    if (!d || !hp) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "gif_write_to_mem: staging of %zu bytes failed", o_out + bound); return nullptr; }
-    for (int l = 0; l < frames; ++l)
-        for (int y = 0; y < h; ++y)
-            memcpy(hp + layer * l + row * y, (const uint8_t*)data + (ptrdiff_t)layer_offset * l + (ptrdiff_t)pitch * y, row);
-    if (hipMemcpyAsync(d, hp, px_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_HIP, "gif_write_to_mem: upload failed"); return nullptr; }
-    const uint8_t* src = d; const int64_t spitch = (int64_t)row, slayer = (int64_t)layer, off = (int64_t)o_out; int64_t n = 0; int status = 0;
     const int32_t W = w, H = h, F = frames, CS = centiseconds, MD = max_bit_depth, AT = alpha_threshold;
-    int rc;
-    try { rc = encode_batch(&src, &spitch, &slayer, &W, &H, &F, &CS, &MD, &AT, 1, &off, d, &n, &status, st); }
-    catch (...) { rc = set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "gif_write_to_mem: out of host memory"); }
-    if (rc != GAMUT_HIP_OK) return nullptr;
-    uint8_t* result = (uint8_t*)malloc((size_t)n);
-    if (!result) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "gif_write_to_mem: out of memory"); return nullptr; }
-    if (hipMemcpyAsync(result, d + o_out, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(result); set_error(GAMUT_HIP_ERR_HIP, "gif_write_to_mem: copy back failed"); return nullptr;
-    }
-    *out_len = (int)n;
-    return result;
+    return encode_host_image("gif_write_to_mem", HostRows{ data, pitch, (size_t)w * 4, h, frames, layer_offset }, (size_t)bound64, out_len,
+        [&](const uint8_t* src, int64_t spitch, int64_t slayer, int64_t off, uint8_t* d, int64_t* n, hipStream_t st) {
+            int status = 0;
+            return encode_batch(&src, &spitch, &slayer, &W, &H, &F, &CS, &MD, &AT, 1, &off, d, n, &status, st);
+        });
 }
 
 float gamut_hip_gif_last_encode_kernel_ms(int which) { return which >= 0 && which < 5 ? t_last_ms[which] : -1.0f; }

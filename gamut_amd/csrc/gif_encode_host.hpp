@@ -39,9 +39,9 @@ int64_t gifenc_frame_reservation(int w, int h);                     // msf_gif.d
 int64_t gifenc_bound(int w, int h, int frames);                     // 0 when refused
 GifEncMul gifenc_mul_table();
 
-// gif_encode.hip: the five launches of one call, asynchronous on `stream`; ev (may be NULL): 6 events recorded around them
+// gif_encode.hip: the five launches of one call, asynchronous on `stream`, with the timer's 6 marks around them
 int gifenc_launch(const GifEncAnim* anims, int n_anim, const GifEncFrame* frames, uint32_t n_frames, uint32_t census_units, uint32_t gather_units,
                   uint32_t* bitmaps, uint32_t* transp, GifEncPlan* plans, uint8_t* slots, int64_t* total_len, uint8_t* out, const GifEncMul& mul,
-                  hipStream_t stream, hipEvent_t* ev);
+                  hipStream_t stream, KernelTimer<6>& timer);
 
 } // namespace gamut

@@ -14,7 +14,7 @@
 //
 // Pixel storage is host malloc memory, as in the reference.  Every pixel operation goes to the GPU through
 // the C ABI of gamut_hip.h (host drop-ins); nothing is computed on the CPU here.
-#include "common.hpp"
+#include "encode_host.hpp"
 #include "../../include/gamut_image.h"
 #include <new>
 
@@ -41,6 +41,10 @@ const char* const kStrInvalidNegLayerOffset    = "Invalid negative layer offset"
 constexpr int  MAX_W = 16777216, MAX_H = 16777216, MAX_LAYERS = 4194303;          // types.d:103-110
 constexpr long long MAX_BYTES = 34359738368LL;                                     // types.d:117
 constexpr int  BORDER_MASK = 384;
+constexpr float kInchesPerMeter = 39.37007874f;                                    // convertInchesToMeters / convertMetersToInches (types.d:126-135)
+// components -> the 8-bit / 16-bit PixelType a decoder hands back
+constexpr int kType8[5]  = { -1, GAMUT_PIXEL_l8, GAMUT_PIXEL_la8, GAMUT_PIXEL_rgb8, GAMUT_PIXEL_rgba8 };
+constexpr int kType16[5] = { -1, GAMUT_PIXEL_l16, GAMUT_PIXEL_la16, GAMUT_PIXEL_rgb16, GAMUT_PIXEL_rgba16 };
 
 // ---- layout constraint helpers (internals/types.d:166-289) ----
 int layoutMultiplicity(int c)      { return 1 << (c & 3); }
@@ -188,6 +192,32 @@ bool allocatePixelStorage(uint8_t* existing, int type, int layers, int width, in
     return true;
 }
 
+// The device-image tail of every save_*: the pixels are encoded where they are, into the thread's encode scratch (`bound` bytes), and
+// the stream comes back in malloc memory.  encode(out, &n, stream) is the codec's batch entry on a batch of one at out_offset 0.
+template <class Encode> uint8_t* encode_device_image(size_t bound, size_t* len, Encode encode)
+{
+    hipStream_t st = thread_stream();
+    uint8_t* d = encode_staging(bound, 0, st, nullptr);
+    if (!d) return nullptr;
+    int64_t n = 0;
+    if (encode(d, &n, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
+    uint8_t* r = (uint8_t*)malloc((size_t)n);
+    if (!r) return nullptr;
+    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipGetLastError(); free(r); return nullptr;
+    }
+    *len = (size_t)n;
+    return r;
+}
+
+bool write_file(const char* path, const uint8_t* bytes, size_t n)
+{
+    FILE* f = fopen(path, "wb");
+    bool ok = f && fwrite(bytes, 1, n, f) == n;
+    if (f && fclose(f) != 0) ok = false;
+    return ok;
+}
+
 } // namespace
 
 // fields in the reference's declaration order (image.d:1573-1620)
@@ -303,6 +333,17 @@ struct gamut_image {
     }
 
     static uint8_t* dmalloc(size_t n) { void* p = nullptr; return hipMalloc(&p, n ? n : 1) == hipSuccess ? (uint8_t*)p : nullptr; }
+    // nbytes a decoder left in the device allocation `dev`: the pixels of a device image as they are; a host image gets a malloc'd
+    // copy and dev is freed.  NULL (and nothing left to free) when the copy cannot be had.
+    uint8_t* residentOrHostCopy(uint8_t* dev, size_t nbytes) const
+    {
+        if (_device) return dev;
+        uint8_t* host = (uint8_t*)malloc(nbytes ? nbytes : 1);
+        const bool ok = host && gamut_hip_memcpy_d2h(host, dev, nbytes, nullptr) == GAMUT_HIP_OK && gamut_hip_stream_synchronize(nullptr) == GAMUT_HIP_OK;
+        (void)hipFree(dev);
+        if (!ok) { free(host); host = nullptr; }
+        return host;
+    }
 
     // decompress_jpeg_image_from_stream with the result left in HBM: host feeder + coefficient upload, then the reconstruction kernels
     uint8_t* decodeJpegToDevice(const uint8_t* bytes, size_t len, int* w, int* h, int* actual, float* aspect, float* dpiY, int req)
@@ -382,10 +423,8 @@ struct gamut_image {
         if (requested != 0) comps = requested;
         if (!decoded) { error(kStrImageDecodingFailed); return; }
         if (!imageIsValidSize(1, w, h)) { error(kStrImageTooLarge); release(decoded); return; }
-        static const int t8[5] = { -1, GAMUT_PIXEL_l8, GAMUT_PIXEL_la8, GAMUT_PIXEL_rgb8, GAMUT_PIXEL_rgba8 };
-        static const int t16[5] = { -1, GAMUT_PIXEL_l16, GAMUT_PIXEL_la16, GAMUT_PIXEL_rgb16, GAMUT_PIXEL_rgba16 };
-        adopt(decoded, w, h, (to16 ? t16 : t8)[comps], comps * (to16 ? 2 : 1), ratio == -1 ? -1.0f : ratio,
-              ppmY == -1 ? -1.0f : ppmY / 39.37007874f);                                    // convertInchesToMeters (types.d:126-129)
+        adopt(decoded, w, h, (to16 ? kType16 : kType8)[comps], comps * (to16 ? 2 : 1), ratio == -1 ? -1.0f : ratio,
+              ppmY == -1 ? -1.0f : ppmY / kInchesPerMeter);
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);
     }
     void loadQOI(const uint8_t* bytes, size_t len, int flags)                               // plugins/qoi.d:47-141
@@ -431,17 +470,11 @@ struct gamut_image {
             if (dev) (void)hipFree(dev);
             error(kStrImageDecodingFailed); return;
         }
-        uint8_t* decoded = dev;
-        if (!_device) {
-            decoded = (uint8_t*)malloc(nbytes ? nbytes : 1);
-            const bool ok = decoded && gamut_hip_memcpy_d2h(decoded, dev, nbytes, nullptr) == GAMUT_HIP_OK && gamut_hip_stream_synchronize(nullptr) == GAMUT_HIP_OK;
-            (void)hipFree(dev);
-            if (!ok) { free(decoded); error(kStrImageDecodingFailed); return; }
-        }
+        uint8_t* decoded = residentOrHostCopy(dev, nbytes);
+        if (!decoded) { error(kStrImageDecodingFailed); return; }
         if (!imageIsValidSize(1, info.width, info.height)) { error(kStrImageTooLarge); release(decoded); return; }
-        static const int t8[5] = { -1, GAMUT_PIXEL_l8, GAMUT_PIXEL_la8, GAMUT_PIXEL_rgb8, GAMUT_PIXEL_rgba8 };
-        adopt(decoded, info.width, info.height, t8[comps], comps, info.pixel_aspect_ratio == -1 ? -1.0f : info.pixel_aspect_ratio,
-              info.pixels_per_meter_y == -1 ? -1.0f : info.pixels_per_meter_y / 39.37007874f);          // :134-135, convertInchesToMeters
+        adopt(decoded, info.width, info.height, kType8[comps], comps, info.pixel_aspect_ratio == -1 ? -1.0f : info.pixel_aspect_ratio,
+              info.pixels_per_meter_y == -1 ? -1.0f : info.pixels_per_meter_y / kInchesPerMeter);          // :134-135
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);
     }
     void loadTGA(const uint8_t* bytes, size_t len, int flags)                               // plugins/tga.d:42-95
@@ -460,15 +493,9 @@ struct gamut_image {
             if (dev) (void)hipFree(dev);
             error(kStrImageDecodingFailed); return;
         }
-        uint8_t* decoded = dev;
-        if (!_device) {
-            decoded = (uint8_t*)malloc(nbytes ? nbytes : 1);
-            const bool ok = decoded && gamut_hip_memcpy_d2h(decoded, dev, nbytes, nullptr) == GAMUT_HIP_OK && gamut_hip_stream_synchronize(nullptr) == GAMUT_HIP_OK;
-            (void)hipFree(dev);
-            if (!ok) { free(decoded); error(kStrImageDecodingFailed); return; }
-        }
-        static const int t8[5] = { -1, GAMUT_PIXEL_l8, GAMUT_PIXEL_la8, GAMUT_PIXEL_rgb8, GAMUT_PIXEL_rgba8 };
-        adopt(decoded, hd.width, hd.height, t8[comps], comps, -1.0f, -1.0f);                // :87-88 GAMUT_UNKNOWN_ASPECT_RATIO / _RESOLUTION
+        uint8_t* decoded = residentOrHostCopy(dev, nbytes);
+        if (!decoded) { error(kStrImageDecodingFailed); return; }
+        adopt(decoded, hd.width, hd.height, kType8[comps], comps, -1.0f, -1.0f);                // :87-88 GAMUT_UNKNOWN_ASPECT_RATIO / _RESOLUTION
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);                           // :94
     }
     // Layers of tight top-down rgba8 rows (device memory) into the image's own storage, whatever pitch and layer offset its constraints gave it
@@ -712,21 +739,10 @@ static uint8_t* save_qoi(gamut_image* img, size_t* len)
         return r;
     }
     // device pixels: encoded where they are, the stream comes back
-    const size_t bound = (size_t)gamut_hip_qoi_encode_bound(&desc);
-    hipStream_t st = thread_stream();
-    static thread_local PerDevice<DeviceScratch> out_pd;
-    uint8_t* d = nullptr;
-    try { d = (uint8_t*)out_pd.cur().get(bound, st); } catch (...) { d = nullptr; }
-    if (!d) return nullptr;
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
-    if (gamut_hip_qoi_encode_batch_device(&src, &pitch, &desc, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
-    uint8_t* r = (uint8_t*)malloc((size_t)n);
-    if (!r) return nullptr;
-    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(r); return nullptr;
-    }
-    *len = (size_t)n;
-    return r;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
+    return encode_device_image((size_t)gamut_hip_qoi_encode_bound(&desc), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
+        return gamut_hip_qoi_encode_batch_device(&src, &pitch, &desc, 1, &off, d, n, &status, st);
+    });
 }
 
 // saveJPEG: l8 -> 1 component, rgb8 -> 3, everything else (rgba8 included: stb would drop the alpha) refused; quality 90 (4:2:0)
@@ -751,22 +767,11 @@ static uint8_t* save_jpeg(gamut_image* img, size_t* len)
         *len = sink.b.size();
         return r;
     }
-    const size_t bound = (size_t)gamut_hip_jpeg_encode_bound(w, h, comp, quality);
-    hipStream_t st = thread_stream();
-    static thread_local PerDevice<DeviceScratch> out_pd;
-    uint8_t* d = nullptr;
-    try { d = (uint8_t*)out_pd.cur().get(bound, st); } catch (...) { d = nullptr; }
-    if (!d) return nullptr;
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
     const int32_t W = w, H = h, Cc = comp, Q = quality;
-    if (gamut_hip_jpeg_encode_batch_device(&src, &pitch, &W, &H, &Cc, &Q, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
-    uint8_t* r = (uint8_t*)malloc((size_t)n);
-    if (!r) return nullptr;
-    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(r); return nullptr;
-    }
-    *len = (size_t)n;
-    return r;
+    return encode_device_image((size_t)gamut_hip_jpeg_encode_bound(w, h, comp, quality), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
+        return gamut_hip_jpeg_encode_batch_device(&src, &pitch, &W, &H, &Cc, &Q, 1, &off, d, n, &status, st);
+    });
 }
 
 // savePNG (plugins/png.d:172-221): the eight integer types, flags read (:201-206), pitch passed through as stb's signed stride
@@ -796,22 +801,11 @@ static uint8_t* save_png(gamut_image* img, int flags, size_t* len)
         if (r) *len = (size_t)n;
         return r;
     }
-    const size_t bound = (size_t)gamut_hip_png_encode_bound(w, h, comp, is16);
-    hipStream_t st = thread_stream();
-    static thread_local PerDevice<DeviceScratch> out_pd;
-    uint8_t* d = nullptr;
-    try { d = (uint8_t*)out_pd.cur().get(bound, st); } catch (...) { d = nullptr; }
-    if (!d) return nullptr;
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
     const int32_t W = w, H = h, Cc = comp, S = is16, F = force_filter, Lv = level;
-    if (gamut_hip_png_encode_batch_device(&src, &pitch, &W, &H, &Cc, &S, &F, &Lv, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
-    uint8_t* r = (uint8_t*)malloc((size_t)n);
-    if (!r) return nullptr;
-    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(r); return nullptr;
-    }
-    *len = (size_t)n;
-    return r;
+    return encode_device_image((size_t)gamut_hip_png_encode_bound(w, h, comp, is16), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
+        return gamut_hip_png_encode_batch_device(&src, &pitch, &W, &H, &Cc, &S, &F, &Lv, 1, &off, d, n, &status, st);
+    });
 }
 
 uint8_t* gamut_image_save_png_to_memory(gamut_image* img, int flags, size_t* len)
@@ -826,9 +820,7 @@ int gamut_image_save_png_to_file(gamut_image* img, const char* path, int flags)
     size_t n = 0;
     uint8_t* enc = gamut_image_save_png_to_memory(img, flags, &n);
     if (!enc) return 0;
-    FILE* f = fopen(path, "wb");
-    bool ok = f && fwrite(enc, 1, n, f) == n;
-    if (f && fclose(f) != 0) ok = false;
+    const bool ok = write_file(path, enc, n);
     free(enc);
     return ok;
 }
@@ -842,8 +834,8 @@ static uint8_t* save_bmp(gamut_image* img, size_t* len)
     // pixelsPerMeterY = convertMetersToInches(dotsPerInchY), X through the aspect ratio (image.d:314-361)
     int ppm_x = 0, ppm_y = 0;
     if (img->_resolutionY != -1) {
-        ppm_y = (int)roundf(img->_resolutionY * 39.37007874f);
-        if (img->_pixelAspectRatio != -1) ppm_x = (int)roundf(img->_resolutionY * img->_pixelAspectRatio * 39.37007874f);
+        ppm_y = (int)roundf(img->_resolutionY * kInchesPerMeter);
+        if (img->_pixelAspectRatio != -1) ppm_x = (int)roundf(img->_resolutionY * img->_pixelAspectRatio * kInchesPerMeter);
     }
     if (!img->_device) {
         int n = 0;
@@ -851,22 +843,11 @@ static uint8_t* save_bmp(gamut_image* img, size_t* len)
         if (r) *len = (size_t)n;
         return r;
     }
-    const size_t bound = (size_t)gamut_hip_bmp_encode_bound(w, h, comp);
-    hipStream_t st = thread_stream();
-    static thread_local PerDevice<DeviceScratch> out_pd;
-    uint8_t* d = nullptr;
-    try { d = (uint8_t*)out_pd.cur().get(bound, st); } catch (...) { d = nullptr; }
-    if (!d) return nullptr;
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
     const int32_t W = w, H = h, Cc = comp, PX = ppm_x, PY = ppm_y;
-    if (gamut_hip_bmp_encode_batch_device(&src, &pitch, &W, &H, &Cc, &PX, &PY, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
-    uint8_t* r = (uint8_t*)malloc((size_t)n);
-    if (!r) return nullptr;
-    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(r); return nullptr;
-    }
-    *len = (size_t)n;
-    return r;
+    return encode_device_image((size_t)gamut_hip_bmp_encode_bound(w, h, comp), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
+        return gamut_hip_bmp_encode_batch_device(&src, &pitch, &W, &H, &Cc, &PX, &PY, 1, &off, d, n, &status, st);
+    });
 }
 
 // saveGIF (plugins/gif.d:105-147): rgba8 only, every layer a frame of 7 centiseconds, maxBitDepth 16, alpha threshold 10
@@ -882,21 +863,11 @@ static uint8_t* save_gif(gamut_image* img, size_t* len)
         if (r) *len = (size_t)n;
         return r;
     }
-    hipStream_t st = thread_stream();
-    static thread_local PerDevice<DeviceScratch> out_pd;
-    uint8_t* d = nullptr;
-    try { d = (uint8_t*)out_pd.cur().get((size_t)bound, st); } catch (...) { d = nullptr; }
-    if (!d) return nullptr;
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, layer = img->_layerOffset, off = 0; int64_t n = 0; int status = 0;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, layer = img->_layerOffset, off = 0; int status = 0;
     const int32_t W = w, H = h, F = frames;
-    if (gamut_hip_gif_encode_batch_device(&src, &pitch, &layer, &W, &H, &F, nullptr, nullptr, nullptr, 1, &off, d, &n, &status, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
-    uint8_t* r = (uint8_t*)malloc((size_t)n);
-    if (!r) return nullptr;
-    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(r); return nullptr;
-    }
-    *len = (size_t)n;
-    return r;
+    return encode_device_image((size_t)bound, len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
+        return gamut_hip_gif_encode_batch_device(&src, &pitch, &layer, &W, &H, &F, nullptr, nullptr, nullptr, 1, &off, d, n, &status, st);
+    });
 }
 
 uint8_t* gamut_image_save_bmp_to_memory(gamut_image* img, int flags, size_t* len)
@@ -912,9 +883,7 @@ int gamut_image_save_bmp_to_file(gamut_image* img, const char* path, int flags)
     size_t n = 0;
     uint8_t* enc = gamut_image_save_bmp_to_memory(img, flags, &n);
     if (!enc) return 0;
-    FILE* f = fopen(path, "wb");
-    bool ok = f && fwrite(enc, 1, n, f) == n;
-    if (f && fclose(f) != 0) ok = false;
+    const bool ok = write_file(path, enc, n);
     free(enc);
     return ok;
 }
@@ -935,9 +904,7 @@ int gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int fl
     size_t n = 0;
     uint8_t* enc = gamut_image_save_to_memory(img, fif, flags, &n);
     if (!enc) return 0;
-    FILE* f = fopen(path, "wb");
-    bool ok = f && fwrite(enc, 1, n, f) == n;
-    if (f && fclose(f) != 0) ok = false;
+    const bool ok = write_file(path, enc, n);
     free(enc);
     return ok;
 }

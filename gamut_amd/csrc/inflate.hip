@@ -1194,9 +1194,7 @@ extern "C" int gamut_hip_inflate_batch_device(const gamut_hip_inflate_desc* desc
     clear_error();
     if (count < 0 || (count > 0 && (!descs || !out_len_dev || !status_dev))) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "inflate_batch_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try { return inflate_launch(descs, count, out_len_dev, status_dev, pick_stream(stream)); }
     catch (...) { return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "inflate_batch_device: out of host memory"); }
 }
@@ -1209,9 +1207,7 @@ extern "C" int gamut_hip_inflate_batch_device_sliced(const gamut_hip_inflate_des
     clear_error();
     if (count < 0 || (count > 0 && (!descs || !out_len_dev || !status_dev)) || !slice_bytes) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "inflate_batch_device_sliced: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try {
         hipStream_t st = pick_stream(stream);
         if (int rc = inflate_sliced_begin(descs, count, st)) return rc;

@@ -16,7 +16,8 @@
 // Raw streams are 32-bit words holding their bits MSB first (the first bit of the stream is bit 31 of word 0).
 // The float arithmetic is the reference's operation for operation: the library is built with -ffp-contract=off -fno-fast-math,
 // and nothing here uses an fma builtin.  The quantiser reciprocals (fdtbl) come from the host.
-#include "common.hpp"
+#include "encode_host.hpp"
+#include "device_util.hpp"
 
 namespace gamut {
 namespace {
@@ -74,13 +75,6 @@ struct JImg {
 };
 
 // ---- device helpers ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int jimg_find(const JImg* imgs, int n, uint32_t g)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (imgs[mid].blk0 <= g) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 // block b of an image -> (class, MCU, position in the MCU).  4:2:0: Y(0,0) Y(8,0) Y(0,8) Y(8,8) U V; 4:4:4: Y U V
 __device__ __forceinline__ void jblock_pos(const JImg& im, uint32_t b, uint32_t& mcu, uint32_t& p)
 {
@@ -180,7 +174,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_jenc_fdct(const JImg* imgs, int
         const bool live = g < n_blk;
         JImg im{}; uint32_t mcu = 0, p = 0; int cls = 0;
         if (live) {
-            im = imgs[jimg_find(imgs, n_img, g)];
+            im = imgs[find_unit<&JImg::blk0>(imgs, n_img, g)];
             jblock_pos(im, g - im.blk0, mcu, p);
             cls = jblock_class(im, p);
             const uint32_t my = mcu / im.mcux, mx = mcu - my * im.mcux;
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_jenc_emit(const JImg* imgs, int
         __syncthreads();
         uint64_t B = 0; uint32_t nw = 0, span = 0; int ii = 0;
         if (live) {
-            ii = jimg_find(imgs, n_img, g);
+            ii = find_unit<&JImg::blk0>(imgs, n_img, g);
             const JImg& im = imgs[ii];
             const uint32_t b = g - im.blk0;
             uint32_t mcu, p; jblock_pos(im, b, mcu, p);
@@ -501,12 +495,11 @@ int jencode_chunk(std::vector<JImg>& imgs, const std::vector<JQual>& quals, cons
         rw = (rw + 3) & ~3ull;                                                 // 16-byte loads in the stuffing passes
     }
     const uint32_t G = (uint32_t)std::max(1, std::min(64, 8192 / n));
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_img = 0, o_q = up(n * sizeof(JImg)), o_hf = o_q + up(quals.size() * sizeof(JQual)), o_coef = o_hf + up(sizeof(JHuff)),
-                 o_dc = o_coef + up(nb * 128), o_acb = o_dc + up(nb * 4), o_off = o_acb + up(nb * 4), o_t = o_off + up(nb * 8),
-                 o_cnt = o_t + up((size_t)n * 8), o_len = o_cnt + up((size_t)n * G * 4), o_raw = o_len + up((size_t)n * 8),
-                 total = o_raw + up(rw * 4 + 16);
-    const size_t h_up = o_coef, h_len = up(h_up);
+    const size_t o_img = 0, o_q = up256(n * sizeof(JImg)), o_hf = o_q + up256(quals.size() * sizeof(JQual)), o_coef = o_hf + up256(sizeof(JHuff)),
+                 o_dc = o_coef + up256(nb * 128), o_acb = o_dc + up256(nb * 4), o_off = o_acb + up256(nb * 4), o_t = o_off + up256(nb * 8),
+                 o_cnt = o_t + up256((size_t)n * 8), o_len = o_cnt + up256((size_t)n * G * 4), o_raw = o_len + up256((size_t)n * 8),
+                 total = o_raw + up256(rw * 4 + 16);
+    const size_t h_up = o_coef, h_len = up256(h_up);
     static thread_local PerDevice<DeviceScratch> scratch_pd;
     static thread_local PerDevice<PinnedScratch> pinned_pd;
     uint8_t* d = (uint8_t*)scratch_pd.cur().get(total, stream);
@@ -573,13 +566,6 @@ int jencode_batch(const uint8_t* const* src, const int64_t* src_pitch, const int
     return GAMUT_HIP_OK;
 }
 
-bool jhave_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return false; }
-    return true;
-}
-
 } // namespace
 } // namespace gamut
 
@@ -597,7 +583,7 @@ int gamut_hip_jpeg_encode_batch_device(const uint8_t* const* src, const int64_t*
     if (count < 0 || (count > 0 && (!src || !src_pitch || !width || !height || !comp || !out_offset || !out || !out_len)))
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "jpeg_encode_batch_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    if (!jhave_device()) return GAMUT_HIP_ERR_NO_DEVICE;
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try {
         return jencode_batch(src, src_pitch, width, height, comp, quality, count, out_offset, out, out_len, status_host, pick_stream(stream));
     } catch (...) {
@@ -610,30 +596,13 @@ void* gamut_hip_jpeg_encode(const void* data, int width, int height, int comp, i
 {
     clear_error();
     if (!data || !out_len || !jvalid(width, height, comp)) { set_error(GAMUT_HIP_ERR_INVALID_ARG, "jpeg_encode: invalid arguments"); return nullptr; }
-    if (!jhave_device()) return nullptr;
-    const size_t row = (size_t)width * comp, px_bytes = row * height, bound = (size_t)jbound(width, height, comp, quality);
-    const size_t o_out = (px_bytes + 255) & ~(size_t)255;
-    hipStream_t st = thread_stream();
-    static thread_local PerDevice<DeviceScratch> dev_pd;
-    static thread_local PerDevice<PinnedScratch> pinned_pd;
-    uint8_t* d = nullptr; uint8_t* h = nullptr;
-    try { d = (uint8_t*)dev_pd.cur().get(o_out + bound, st); h = pinned_pd.cur().get(px_bytes, st); } catch (...) { d = nullptr; }
-    if (!d || !h) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "jpeg_encode: staging of %zu bytes failed", o_out + bound); return nullptr; }
-    for (int y = 0; y < height; ++y) memcpy(h + row * y, (const uint8_t*)data + (ptrdiff_t)pitch * y, row);
-    if (hipMemcpyAsync(d, h, px_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_HIP, "jpeg_encode: upload failed"); return nullptr; }
-    const uint8_t* src = d; const int64_t p = (int64_t)row, off = (int64_t)o_out; int64_t len = 0; int status = 0;
+    if (!have_device()) return nullptr;
     const int32_t w = width, hh = height, c = comp, q = quality;
-    int rc;
-    try { rc = jencode_batch(&src, &p, &w, &hh, &c, &q, 1, &off, d, &len, &status, st); }
-    catch (...) { rc = set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "jpeg_encode: out of host memory"); }
-    if (rc != GAMUT_HIP_OK) return nullptr;
-    uint8_t* result = (uint8_t*)malloc((size_t)len);
-    if (!result) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "jpeg_encode: out of memory"); return nullptr; }
-    if (hipMemcpyAsync(result, d + o_out, (size_t)len, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(result); set_error(GAMUT_HIP_ERR_HIP, "jpeg_encode: copy back failed"); return nullptr;
-    }
-    *out_len = (int)len;
-    return result;
+    return encode_host_image("jpeg_encode", HostRows{ data, pitch, (size_t)width * comp, height, 1, 0 }, (size_t)jbound(width, height, comp, quality), out_len,
+        [&](const uint8_t* src, int64_t p, int64_t, int64_t off, uint8_t* d, int64_t* len, hipStream_t st) {
+            int status = 0;
+            return jencode_batch(&src, &p, &w, &hh, &c, &q, 1, &off, d, len, &status, st);
+        });
 }
 
 // drop-in for stbi_write_jpg_to_func: the whole stream in one call of func

@@ -2310,9 +2310,7 @@ int gamut_hip_jpeg_entropy_decode_device(const uint8_t* const* data, const size_
     if (count < 0 || (count > 0 && (!data || !len || !coeff_offset || !zag_offset || !coeffs || !max_zag || !info)))
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "jpeg_entropy_decode_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try {                                                      // std::vector / bad_alloc must not escape a C entry point
         return entropy_decode_device(data, len, count, coeff_offset, zag_offset, coeffs, max_zag, status_dev, info, status_host, pick_stream(stream));
     } catch (...) {
@@ -2328,9 +2326,7 @@ int gamut_hip_jpeg_decode_batch_device(const uint8_t* const* data, const size_t*
     if (count < 0 || (req_comps != 1 && req_comps != 3 && req_comps != 4) || (count > 0 && (!data || !len || !out_offset || !out || !info)))
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "jpeg_decode_batch_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try {
         hipStream_t st = pick_stream(stream);
         static thread_local PerDevice<DeviceScratch> co_pd, zz_pd, tok_pd, strip_pd, offs_pd;

@@ -18,7 +18,8 @@
 //   5. k_penc_finish : one workgroup per image: zlib header, Adler-32, signature, IHDR, IDAT length and CRC-32 (per-thread
 //                      pieces combined by multiplication with x^(8 len) mod P), IEND, out_len.
 // Stages 2-5 know nothing of PNG beyond the list of candidate distances in the image record.
-#include "common.hpp"
+#include "encode_host.hpp"
+#include "device_util.hpp"
 #include <climits>
 
 namespace gamut {
@@ -46,18 +47,6 @@ struct PImg {
 };
 struct PBlk { uint32_t bits, kind, s1, s2; };         // kind 0 stored, 1 compressed; s1 / s2: Adler partials of the block's bytes
 
-__device__ __forceinline__ int pimg_find_row(const PImg* imgs, int n, uint32_t g)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (imgs[mid].row0 <= g) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-__device__ __forceinline__ int pimg_find_blk(const PImg* imgs, int n, uint32_t g)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (imgs[mid].blk0 <= g) lo = mid; else hi = mid - 1; }
-    return lo;
-}
 __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) { for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) { for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
 
@@ -93,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void k_penc_filter(const PImg* imgs, int 
     __shared__ int chosen;
     const int t = threadIdx.x;
     for (uint32_t g = blockIdx.x; g < n_rows; g += gridDim.x) {
-        const PImg& im = imgs[pimg_find_row(imgs, n_img, g)];
+        const PImg& im = imgs[find_unit<&PImg::row0>(imgs, n_img, g)];
         const uint32_t y = g - im.row0, bps = im.n * (im.is16 ? 2u : 1u), est_n = im.w * im.n;
         const uint8_t* z = im.src + (int64_t)y * im.pitch;
         const bool top = y == 0;
@@ -262,7 +251,7 @@ __global__ __launch_bounds__(kThreads) void k_penc_block(const PImg* imgs, int n
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const uint32_t g = blockIdx.x;
-    const PImg& im = imgs[pimg_find_blk(imgs, n_img, g)];
+    const PImg& im = imgs[find_unit<&PImg::blk0>(imgs, n_img, g)];
     const uint32_t b = g - im.blk0, s0 = b * kBlock, n = min(kBlock, im.L - s0);
     const uint8_t* f = filt + im.filt0;                // the image's filtered stream; the block is f[s0, s0 + n)
     const uint8_t* blk = f + s0;
@@ -521,7 +510,7 @@ __global__ __launch_bounds__(kThreads) void k_penc_place(const PImg* imgs, int n
 {
     const int t = threadIdx.x;
     const uint32_t g = blockIdx.x;
-    const PImg& im = imgs[pimg_find_blk(imgs, n_img, g)];
+    const PImg& im = imgs[find_unit<&PImg::blk0>(imgs, n_img, g)];
     const uint32_t b = g - im.blk0, s0 = b * kBlock, n = min(kBlock, im.L - s0);
     const bool last = b + 1 == im.nblk;
     const uint64_t o = off[g], c = size[g];
@@ -673,10 +662,9 @@ int pencode_chunk(std::vector<PImg>& imgs, const std::vector<int>& which, int64_
         im.row0 = (uint32_t)rows; im.blk0 = (uint32_t)blks; im.filt0 = fb;
         rows += im.h; blks += im.nblk; fb += ((uint64_t)im.L + 15) & ~15ull;
     }
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_img = 0, o_meta = up((size_t)n * sizeof(PImg)), o_off = o_meta + up(blks * sizeof(PBlk)), o_size = o_off + up(blks * 8),
-                 o_t = o_size + up(blks * 8), o_ad = o_t + up((size_t)n * 8), o_len = o_ad + up((size_t)n * 4), o_slots = o_len + up((size_t)n * 8),
-                 o_filt = o_slots + up(blks * kSlotWords * 4), total = o_filt + up(fb + 16);
+    const size_t o_img = 0, o_meta = up256((size_t)n * sizeof(PImg)), o_off = o_meta + up256(blks * sizeof(PBlk)), o_size = o_off + up256(blks * 8),
+                 o_t = o_size + up256(blks * 8), o_ad = o_t + up256((size_t)n * 8), o_len = o_ad + up256((size_t)n * 4), o_slots = o_len + up256((size_t)n * 8),
+                 o_filt = o_slots + up256(blks * kSlotWords * 4), total = o_filt + up256(fb + 16);
     const size_t h_up = o_meta;
     static thread_local PerDevice<DeviceScratch> scratch_pd;
     static thread_local PerDevice<PinnedScratch> pinned_pd;
@@ -741,13 +729,6 @@ int pencode_batch(const uint8_t* const* src, const int64_t* src_pitch, const int
     return GAMUT_HIP_OK;
 }
 
-bool phave_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return false; }
-    return true;
-}
-
 } // namespace
 } // namespace gamut
 
@@ -765,7 +746,7 @@ int gamut_hip_png_encode_batch_device(const uint8_t* const* src, const int64_t* 
     if (count < 0 || (count > 0 && (!src || !src_pitch || !width || !height || !comp || !is16bit || !out_offset || !out || !out_len)))
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "png_encode_batch_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    if (!phave_device()) return GAMUT_HIP_ERR_NO_DEVICE;
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try {
         return pencode_batch(src, src_pitch, width, height, comp, is16bit, force_filter, level, count, out_offset, out, out_len, status_host,
                              pick_stream(stream));
@@ -783,30 +764,13 @@ void* gamut_hip_png_write_to_mem(const void* pixels, int stride_bytes, int x, in
     if (!pixels || !out_len || !pvalid(x, y, n, is16) || compression_level < 0 || compression_level > 10 || pbound(x, y, n, is16) > INT_MAX) {
         set_error(GAMUT_HIP_ERR_INVALID_ARG, "png_write_to_mem: invalid arguments"); return nullptr;
     }
-    if (!phave_device()) return nullptr;
-    const size_t row = (size_t)x * n * (is16 ? 2 : 1), px_bytes = row * y, bound = (size_t)pbound(x, y, n, is16);
-    const size_t o_out = (px_bytes + 255) & ~(size_t)255;
-    hipStream_t st = thread_stream();
-    static thread_local PerDevice<DeviceScratch> dev_pd;
-    static thread_local PerDevice<PinnedScratch> pinned_pd;
-    uint8_t* d = nullptr; uint8_t* h = nullptr;
-    try { d = (uint8_t*)dev_pd.cur().get(o_out + bound, st); h = pinned_pd.cur().get(px_bytes, st); } catch (...) { d = nullptr; }
-    if (!d || !h) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png_write_to_mem: staging of %zu bytes failed", o_out + bound); return nullptr; }
-    for (int r = 0; r < y; ++r) memcpy(h + row * r, (const uint8_t*)pixels + (ptrdiff_t)stride_bytes * r, row);
-    if (hipMemcpyAsync(d, h, px_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_HIP, "png_write_to_mem: upload failed"); return nullptr; }
-    const uint8_t* src = d; const int64_t p = (int64_t)row, off = (int64_t)o_out; int64_t len = 0; int status = 0;
+    if (!have_device()) return nullptr;
     const int32_t w = x, hh = y, c = n, s16 = is16, ff = force_filter, lv = compression_level;
-    int rc;
-    try { rc = pencode_batch(&src, &p, &w, &hh, &c, &s16, &ff, &lv, 1, &off, d, &len, &status, st); }
-    catch (...) { rc = set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png_write_to_mem: out of host memory"); }
-    if (rc != GAMUT_HIP_OK) return nullptr;
-    uint8_t* result = (uint8_t*)malloc((size_t)len);
-    if (!result) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png_write_to_mem: out of memory"); return nullptr; }
-    if (hipMemcpyAsync(result, d + o_out, (size_t)len, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(result); set_error(GAMUT_HIP_ERR_HIP, "png_write_to_mem: copy back failed"); return nullptr;
-    }
-    *out_len = (int)len;
-    return result;
+    return encode_host_image("png_write_to_mem", HostRows{ pixels, stride_bytes, (size_t)x * n * (is16 ? 2 : 1), y, 1, 0 }, (size_t)pbound(x, y, n, is16), out_len,
+        [&](const uint8_t* src, int64_t p, int64_t, int64_t off, uint8_t* d, int64_t* len, hipStream_t st) {
+            int status = 0;
+            return pencode_batch(&src, &p, &w, &hh, &c, &s16, &ff, &lv, 1, &off, d, len, &status, st);
+        });
 }
 
 } // extern "C"

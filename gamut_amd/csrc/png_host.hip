@@ -313,10 +313,9 @@ uint8_t* png_load(const uint8_t* data, size_t len, int* px, int* py, int* pn, in
                   float* ppmX, float* ppmY, float* aspect)
 {
     if (req_comp < 0 || req_comp > 4) { set_error(GAMUT_HIP_ERR_INVALID_ARG, "png: bad req_comp"); return nullptr; }
-    int dev_count = 0;                                                       // before any work: no GPU, no result
     PngHeader probe;
     if (parse(data, len, probe, true)) return nullptr;                       // a bad signature is reported as such with or without a GPU
-    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count <= 0) { set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return nullptr; }
+    if (!have_device()) return nullptr;                                      // before any work: no GPU, no result
     struct Staging { HostBuf b{ nullptr, 0, true }; };
     static thread_local PerDevice<Staging> staging_pd;
     HostBuf& staging = staging_pd.cur().b;
@@ -421,9 +420,8 @@ int gamut_hip_png_decode_batch_device(const uint8_t* const* data, const size_t* 
     if (count < 0 || (count > 0 && (!data || !len || !out_offset || !out || !info)) || req_comp < 0 || req_comp > 4 || (bits != 0 && bits != 8 && bits != 16))
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "png_decode_batch_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
+    int dev = 0;
     (void)hipGetDevice(&dev);
     try {
         if (threads <= 0) threads = host_threads();

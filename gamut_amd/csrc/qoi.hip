@@ -984,9 +984,7 @@ int gamut_hip_qoi_decode_batch_device(const uint8_t* const* data, const int* siz
     if (count < 0 || (count > 0 && (!data || !size || !out_offset || !out || !descs)))
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoi_decode_batch_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try {                                                      // std::vector / bad_alloc must not escape a C entry point
         return decode_batch(data, size, count, channels, out_offset, out, descs, status_host, pick_stream(stream));
     } catch (...) {
@@ -1002,9 +1000,7 @@ int gamut_hip_qoi_decode_resident_device(const uint8_t* blob, int64_t blob_len, 
     if (count < 0 || (channels != 0 && channels != 3 && channels != 4) || (count > 0 && (!blob || !begin || !size || !descs || !out_offset || !out)))
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoi_decode_resident_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try {
         std::vector<QoiItem> items((size_t)count);
         for (int i = 0; i < count; ++i) {
@@ -1064,8 +1060,7 @@ void* gamut_hip_qoi_decode(const void* data, int size, gamut_hip_qoi_desc* desc,
     gamut_hip_qoi_desc local;
     if (!desc) desc = &local;
     if (read_header((const uint8_t*)data, size, desc, channels) != GAMUT_HIP_OK) return nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return nullptr; }
+    if (!have_device()) return nullptr;
     const int ch = channels ? channels : desc->channels;
     const size_t bytes = (size_t)desc->width * desc->height * ch;
     uint8_t* result = (uint8_t*)malloc(bytes ? bytes : 1);

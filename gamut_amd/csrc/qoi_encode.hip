@@ -16,7 +16,8 @@
 //   5. k_enc_walk<1> : the same walk again, writing the bytes (dword stores where the position allows).
 // The input is read three times (1, 3, 5).  Scratch per tile: 64 table words + 16 bytes of summary + 12 bytes of carry / count /
 // offset, about 300 B per 1024 pixels (0.6 MB per 1080p frame).
-#include "common.hpp"
+#include "encode_host.hpp"
+#include "device_util.hpp"
 
 namespace gamut {
 namespace {
@@ -35,14 +36,6 @@ struct EncImg {
 struct TileMeta { uint32_t mask_lo, mask_hi, allrep, trail; };
 
 __device__ __forceinline__ uint32_t enc_hash(uint32_t px) { return __builtin_amdgcn_udot4(px, 0x0B070503u, 0u, false) & 63u; }  // QOI_COLOR_HASH % 64
-
-// the image a tile belongs to: images are in tile order
-__device__ __forceinline__ int enc_find_image(const EncImg* imgs, int n, uint32_t g)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (imgs[mid].tile0 <= g) lo = mid; else hi = mid - 1; }
-    return lo;
-}
 
 // pixel reader: rows of `pitch` bytes (negative allowed), any alignment; 3 channels get alpha 255 (qoi.d:356-366)
 struct EncReader {
@@ -82,7 +75,7 @@ __global__ __launch_bounds__(kLanes) void k_enc_summary(const EncImg* imgs, int 
     const int lane = threadIdx.x;
     const uint32_t g = blockIdx.x * kLanes + lane;
     if (g >= n_tiles) return;
-    const EncImg im = imgs[enc_find_image(imgs, n_img, g)];
+    const EncImg im = imgs[find_unit<&EncImg::tile0>(imgs, n_img, g)];
     const uint32_t p0 = (g - im.tile0) * kTile, len = min((uint32_t)kTile, im.npx - p0);
     uint32_t prev = enc_prev(im, p0), trail = 0, allrep = 1;
     uint64_t mask = 0;
@@ -136,7 +129,7 @@ __global__ __launch_bounds__(kLanes) void k_enc_walk(const EncImg* imgs, int n_i
     const int lane = threadIdx.x;
     const uint32_t g = blockIdx.x * kLanes + lane;
     if (g >= n_tiles) return;
-    const EncImg im = imgs[enc_find_image(imgs, n_img, g)];
+    const EncImg im = imgs[find_unit<&EncImg::tile0>(imgs, n_img, g)];
     const uint32_t p0 = (g - im.tile0) * kTile, len = min((uint32_t)kTile, im.npx - p0), last = im.npx - 1 - p0;
     const uint32_t* t = tab + (size_t)g * 64;
     for (int s = 0; s < 64; ++s) table[s * kLanes + lane] = t[s];
@@ -250,13 +243,12 @@ int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamu
     if (!imgs.empty()) {
         const int n = (int)imgs.size();
         const uint32_t T = (uint32_t)tiles;
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t o_img = 0, o_tab = up(n * sizeof(EncImg)), o_meta = o_tab + up((size_t)T * 256), o_run = o_meta + up((size_t)T * sizeof(TileMeta)),
-                     o_cnt = o_run + up((size_t)T * 4), o_off = o_cnt + up((size_t)T * 4), o_len = o_off + up((size_t)T * 4), total = o_len + up((size_t)n * 8);
+        const size_t o_img = 0, o_tab = up256(n * sizeof(EncImg)), o_meta = o_tab + up256((size_t)T * 256), o_run = o_meta + up256((size_t)T * sizeof(TileMeta)),
+                     o_cnt = o_run + up256((size_t)T * 4), o_off = o_cnt + up256((size_t)T * 4), o_len = o_off + up256((size_t)T * 4), total = o_len + up256((size_t)n * 8);
         static thread_local PerDevice<DeviceScratch> scratch_pd;
         static thread_local PerDevice<PinnedScratch> pinned_pd;
         uint8_t* d = (uint8_t*)scratch_pd.cur().get(total, stream);
-        uint8_t* h = pinned_pd.cur().get(up(n * sizeof(EncImg)) + (size_t)n * 8, stream);
+        uint8_t* h = pinned_pd.cur().get(up256(n * sizeof(EncImg)) + (size_t)n * 8, stream);
         if (!d || !h) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "qoi_encode: scratch allocation of %zu bytes failed", total);
         memcpy(h, imgs.data(), n * sizeof(EncImg));
         GAMUT_HIP_CHECK(hipMemcpyAsync(d + o_img, h, n * sizeof(EncImg), hipMemcpyHostToDevice, stream));
@@ -271,20 +263,13 @@ int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamu
         hipLaunchKernelGGL(k_enc_scan, dim3(n), dim3(kScanThreads), 0, stream, dimg, (const uint32_t*)cnt, off, len, out);
         hipLaunchKernelGGL(k_enc_walk<1>, grid, dim3(kLanes), 0, stream, dimg, n, T, (const uint32_t*)tab, (const uint32_t*)run, (uint32_t*)nullptr, (const uint32_t*)off, out);
         if (int rc = launch_status("qoi_encode")) return rc;
-        int64_t* hlen = (int64_t*)(h + up(n * sizeof(EncImg)));
+        int64_t* hlen = (int64_t*)(h + up256(n * sizeof(EncImg)));
         GAMUT_HIP_CHECK(hipMemcpyAsync(hlen, len, (size_t)n * 8, hipMemcpyDeviceToHost, stream));
         GAMUT_HIP_CHECK(hipStreamSynchronize(stream));
         for (int k = 0; k < n; ++k) out_len[which[(size_t)k]] = hlen[k];
     }
     if (first_bad >= 0) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "image %d: qoi_encode: invalid desc or source", first_bad);
     return GAMUT_HIP_OK;
-}
-
-bool have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return false; }
-    return true;
 }
 
 } // namespace
@@ -317,28 +302,12 @@ void* gamut_hip_qoi_encode(const void* data, const gamut_hip_qoi_desc* desc, int
     clear_error();
     if (!data || !desc || !out_len || encode_bound(desc) == 0) { set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoi_encode: invalid arguments"); return nullptr; }
     if (!have_device()) return nullptr;
-    const size_t row = (size_t)desc->width * desc->channels, px_bytes = row * desc->height, bound = (size_t)encode_bound(desc);
-    const size_t o_out = (px_bytes + 255) & ~(size_t)255;
-    hipStream_t st = thread_stream();
-    static thread_local PerDevice<DeviceScratch> dev_pd;
-    static thread_local PerDevice<PinnedScratch> pinned_pd;
-    uint8_t* d = (uint8_t*)dev_pd.cur().get(o_out + bound, st);
-    uint8_t* h = pinned_pd.cur().get(px_bytes, st);
-    if (!d || !h) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "qoi_encode: staging of %zu bytes failed", o_out + bound); return nullptr; }
-    for (uint32_t y = 0; y < desc->height; ++y) memcpy(h + row * y, (const uint8_t*)data + (ptrdiff_t)pitch_bytes * y, row);
-    if (hipMemcpyAsync(d, h, px_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_HIP, "qoi_encode: upload failed"); return nullptr; }
-    const uint8_t* src = d; const int64_t pitch = (int64_t)row, off = (int64_t)o_out; int64_t len = 0; int status = 0;
-    int rc;
-    try { rc = encode_batch(&src, &pitch, desc, 1, &off, d, &len, &status, st); }
-    catch (...) { rc = set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "qoi_encode: out of host memory"); }
-    if (rc != GAMUT_HIP_OK) return nullptr;
-    uint8_t* result = (uint8_t*)malloc((size_t)len);
-    if (!result) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "qoi_encode: out of memory"); return nullptr; }
-    if (hipMemcpyAsync(result, d + o_out, (size_t)len, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(result); set_error(GAMUT_HIP_ERR_HIP, "qoi_encode: copy back failed"); return nullptr;
-    }
-    *out_len = (int)len;
-    return result;
+    return encode_host_image("qoi_encode", HostRows{ data, pitch_bytes, (size_t)desc->width * desc->channels, (int)desc->height, 1, 0 },
+                             (size_t)encode_bound(desc), out_len,
+        [&](const uint8_t* src, int64_t pitch, int64_t, int64_t off, uint8_t* d, int64_t* len, hipStream_t st) {
+            int status = 0;
+            return encode_batch(&src, &pitch, desc, 1, &off, d, len, &status, st);
+        });
 }
 
 } // extern "C"

@@ -116,6 +116,25 @@ hipStream_t thread_stream()
     return s;
 }
 
+bool have_device()
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) == hipSuccess && n > 0) return true;
+    (void)hipGetLastError();
+    set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
+    return false;
+}
+
+uint8_t* encode_staging(size_t device_bytes, size_t pinned_bytes, hipStream_t stream, uint8_t** pinned)
+{
+    static thread_local PerDevice<DeviceScratch> dev_pd;
+    static thread_local PerDevice<PinnedScratch> pinned_pd;
+    try {
+        if (pinned && !(*pinned = pinned_pd.cur().get(pinned_bytes, stream))) return nullptr;
+        return static_cast<uint8_t*>(dev_pd.cur().get(device_bytes, stream));
+    } catch (...) { return nullptr; }                         // PerDevice<>::cur() throws std::bad_alloc
+}
+
 namespace {
 
 // RAII device buffer for the synchronous host entry points
@@ -129,14 +148,6 @@ struct DevBuf {
     }
 };
 
-int require_device()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)");
-    return GAMUT_HIP_OK;
-}
-
 // Host drop-in shared by convert and copy: stage the rectangle through tight HBM buffers.
 int host_convert(int srcType, const uint8_t* src, int srcPitch, int dstType, uint8_t* dst, int dstPitch, int width, int height)
 {
@@ -145,7 +156,7 @@ int host_convert(int srcType, const uint8_t* src, int srcPitch, int dstType, uin
     if (width < 0 || height < 0) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "scanlinesConvert: negative size");
     if (width == 0 || height == 0) return GAMUT_HIP_OK;
     if (!src || !dst) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "scanlinesConvert: null pointer");
-    if (int rc = require_device()) return rc;
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
 
     const size_t srow = (size_t)width * kPixelSize[srcType], drow = (size_t)width * kPixelSize[dstType];
     const size_t sabs = (size_t)(srcPitch < 0 ? -(int64_t)srcPitch : srcPitch), dabs = (size_t)(dstPitch < 0 ? -(int64_t)dstPitch : dstPitch);
@@ -190,7 +201,7 @@ int gamut_hip_device_count(void)
 int gamut_hip_init(int device)
 {
     clear_error();
-    if (int rc = require_device()) return rc;
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     if (device >= 0) GAMUT_HIP_CHECK(hipSetDevice(device));
     GAMUT_HIP_CHECK(hipFree(nullptr));      // force context creation
     return GAMUT_HIP_OK;

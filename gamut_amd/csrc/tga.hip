@@ -27,6 +27,7 @@
 // Kept from the reference: the colour map starts palette_start BYTES behind the ID field; 15 / 16-bit entries and pixels are not
 // R/B swapped; 16-bit grey is two raw bytes.  DEVIATION: width * height * components > 2^31 - 1 is refused (tga_host.hip).
 #include "common.hpp"
+#include "device_util.hpp"
 
 namespace gamut {
 int tga_parse_header(const uint8_t* data, size_t len, gamut_hip_tga_info* info);                   // tga_host.hip
@@ -50,22 +51,6 @@ struct TgaImg {
     uint32_t status;                                                         // RLE: index of the file's status word
     uint8_t  bps, comps, outc, indexed, rgb16, bottom_up, pal_esz, pad;      // bps: bytes per source pixel; comps: the file's; outc: stored
 };
-
-__device__ __forceinline__ int find_image(const TgaImg* imgs, int n, uint32_t u)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (imgs[mid].unit0 <= u) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
-// the aligned dword at file position pos (a multiple of 4); a dword that begins inside the file ends inside the blob
-__device__ __forceinline__ uint32_t file_dword(const TgaImg& im, uint64_t pos)
-{
-    return pos < im.avail ? *reinterpret_cast<const uint32_t*>(im.file + pos) : 0u;
-}
-__device__ __forceinline__ uint32_t file_byte(const TgaImg& im, uint64_t pos) { return pos < im.avail ? im.file[pos] : 0u; }
-
-__device__ __forceinline__ uint32_t byte_of(const uint32_t* v, uint32_t k) { return (v[k >> 2] >> (8 * (k & 3))) & 255u; }
 
 // n bytes of the file from position `from` (any alignment) into LDS dwords S[0 ..): aligned loads, v_alignbyte_b32
 __device__ __forceinline__ void stage_bytes(const TgaImg& im, uint64_t from, uint32_t n, uint32_t* S, uint32_t tid)
@@ -122,30 +107,13 @@ __device__ __forceinline__ uint32_t pixel(const TgaImg& im, const uint32_t* pal,
     return px;
 }
 
-// A run of n bytes that a workgroup has assembled in LDS (S, dword array, spare dwords behind the run) goes to dst, which may have
-// any alignment: head up to the first 16-byte boundary and tail by bytes, the body as aligned 16-byte stores (bmp.hip's flush_run)
-__device__ __forceinline__ void flush_run(const uint32_t* S, uint8_t* dst, uint32_t n, uint32_t tid)
-{
-    const uint32_t head = min(n, (uint32_t)((16u - ((uintptr_t)dst & 15u)) & 15u));
-    if (tid < head) dst[tid] = (uint8_t)byte_of(S, tid);
-    const uint32_t chunks = (n - head) >> 4;
-    for (uint32_t c = tid; c < chunks; c += kThreads) {
-        const uint32_t r = head + 16u * c, i = r >> 2, sh = r & 3u;
-        const uint32_t a0 = S[i], a1 = S[i + 1], a2 = S[i + 2], a3 = S[i + 3], a4 = S[i + 4];
-        *reinterpret_cast<uint4*>(dst + r) = make_uint4(__builtin_amdgcn_alignbyte(a1, a0, sh), __builtin_amdgcn_alignbyte(a2, a1, sh),
-                                                        __builtin_amdgcn_alignbyte(a3, a2, sh), __builtin_amdgcn_alignbyte(a4, a3, sh));
-    }
-    const uint32_t t = head + 16u * chunks + tid;
-    if (t < n) dst[t] = (uint8_t)byte_of(S, t);
-}
-
 __global__ __launch_bounds__(kThreads) void k_tga_unpacked(const TgaImg* imgs, int n_img, uint8_t* out)
 {
     __shared__ uint32_t pal[kPalLds];
     __shared__ uint32_t src[kSegPx + 4];                                     // the unit's source bytes: 1024 pixels x up to 4
     __shared__ uint32_t run[kSegPx + 8];                                     // the unit's output bytes
     const uint32_t u = blockIdx.x, tid = threadIdx.x;
-    const TgaImg im = imgs[find_image(imgs, n_img, u)];
+    const TgaImg im = imgs[find_unit<&TgaImg::unit0>(imgs, n_img, u)];
     const uint32_t lu = u - im.unit0, j = lu / im.segs, seg = lu - j * im.segs;
     const uint32_t x0 = seg * kSegPx, npx = min((uint32_t)kSegPx, im.w - x0);   // (uniform over the workgroup)
     load_palette(im, pal, tid);
@@ -164,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void k_tga_unpacked(const TgaImg* imgs, i
     }
     __syncthreads();
     const uint32_t y = im.bottom_up ? im.h - 1 - j : j;                      // :426 / :557-572
-    flush_run(run, out + im.out_off + ((uint64_t)y * im.w + x0) * im.outc, npx * im.outc, tid);
+    flush_run<kThreads>(run, out + im.out_off + ((uint64_t)y * im.w + x0) * im.outc, npx * im.outc, tid);
 }
 
 __device__ __forceinline__ uint32_t packet_pixels(uint32_t cmd) { return (cmd & 127u) + 1u; }
@@ -259,20 +227,9 @@ __global__ __launch_bounds__(kThreads) void k_tga_rle(const TgaImg* imgs, uint8_
     }
 }
 
-bool have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); set_error(GAMUT_HIP_ERR_NO_DEVICE, "no HIP device available (libgamut_hip has no CPU fallback)"); return false; }
-    return true;
-}
-
 // Measurements (tools/tga_bench.py): with GAMUT_HIP_TGA_TIMING=1 the decode call brackets its kernels -- not the upload -- with events
 // and keeps the GPU time of the calling thread's last call; the blob is resident in HBM when the first event is reached.
 thread_local float t_last_decode_kernel_ms = -1.0f;
-bool timing_on() { static const bool on = [] { const char* e = getenv("GAMUT_HIP_TGA_TIMING"); return e && *e && atoi(e) != 0; }(); return on; }
-
-size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int decode_batch(const uint8_t* const* data, const size_t* len, int count, int req_comp, const int64_t* out_offset, uint8_t* out,
                  gamut_hip_tga_info* info, int* status_host, hipStream_t stream)
@@ -349,19 +306,16 @@ int decode_batch(const uint8_t* const* data, const size_t* len, int count, int r
         if (nf) memcpy(h + o_flat, flat.data(), nf * sizeof(TgaImg));
         if (nr) memcpy(h + o_rle, rle.data(), nr * sizeof(TgaImg));
         GAMUT_HIP_CHECK(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, stream));
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (timing_on() && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess || hipEventRecord(ev0, stream) != hipSuccess)) {
-            (void)hipGetLastError(); ev0 = nullptr;
-        }
+        static const bool timing = env_flag("GAMUT_HIP_TGA_TIMING");
+        KernelTimer<2> timer(timing);
+        timer.mark(stream);
         if (nf) hipLaunchKernelGGL(k_tga_unpacked, dim3((uint32_t)units), dim3(kThreads), 0, stream, (const TgaImg*)(d + o_flat), (int)nf, out);
         if (nr) hipLaunchKernelGGL(k_tga_rle, dim3((uint32_t)nr), dim3(kThreads), 0, stream, (const TgaImg*)(d + o_rle), out, (uint32_t*)(d + o_st));
         if (int rc = launch_status("tga_decode")) return rc;
-        if (ev0) (void)hipEventRecord(ev1, stream);
+        timer.mark(stream);
         if (nr) GAMUT_HIP_CHECK(hipMemcpyAsync(h + o_st, d + o_st, nr * 4, hipMemcpyDeviceToHost, stream));
         GAMUT_HIP_CHECK(hipStreamSynchronize(stream));
-        if (ev0) { if (hipEventElapsedTime(&t_last_decode_kernel_ms, ev0, ev1) != hipSuccess) { (void)hipGetLastError(); t_last_decode_kernel_ms = -1.0f; } }
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
+        timer.finish(&t_last_decode_kernel_ms);
         const uint32_t* st = (const uint32_t*)(h + o_st);
         for (size_t k = 0; k < nr; ++k)
             if (st[k]) { tga_fail("run-length stream ends before width * height pixels"); refuse(which_rle[k], GAMUT_HIP_ERR_DECODE); }

@@ -128,6 +128,33 @@ def test_all_a_rule(L, w, h):
             assert (refs[0][0][..., 1] == 255).all() and (refs[3][0][..., 1] == 0).all()
 
 
+def test_decode_runs_at_every_output_alignment(L):
+    """a row of 1 pixel (3 bytes: shorter than the 16-byte head of its store), of 5 (head and tail, no 16-byte body) and of 1025 (one
+    pixel into a second 1024-pixel unit) in one batch of three 2-row files at req_comp 3, with EVERY out_offset at residue r modulo 16,
+    r = 0..15 in turn; the whole allocation, canaries between and around the images included, against the reference"""
+    files = [bmp_gen.make(w, 2, 24, 40, top_down=w == 5, seed=w) for w in (1, 5, 1025)]
+    refs = [bmp_ref_c.load(f, 3)[0] for f in files]
+    assert [r.shape for r in refs] == [(2, 1, 3), (2, 5, 3), (2, 1025, 3)]
+    bufs = [np.frombuffer(f, np.uint8) for f in files]
+    ptrs = (C.c_void_p * 3)(*[b.ctypes.data for b in bufs]); lens = (C.c_size_t * 3)(*[b.size for b in bufs])
+    for r in range(16):
+        offs, pos = [], 0
+        for ref in refs:
+            pos = (pos + 64 + 15) // 16 * 16 + r                            # at least 64 canary bytes in front of every image
+            offs.append(pos); pos += ref.size
+        pos += 64
+        expect = np.full(pos, 0xA5, np.uint8)
+        for ref, o in zip(refs, offs):
+            expect[o:o + ref.size] = ref.reshape(-1)
+        out = torch.full((pos,), 0xA5, dtype=torch.uint8, device="cuda")
+        assert out.data_ptr() % 16 == 0 and all(o % 16 == r for o in offs)
+        info = (_capi.BmpInfo * 3)(); st = (C.c_int * 3)(77, 77, 77)
+        rc = L.gamut_hip_bmp_decode_batch_device(ptrs, lens, 3, 3, (C.c_int64 * 3)(*offs), out.data_ptr(), info, st, None)
+        assert rc == 0 and list(st) == [0, 0, 0], (r, L.gamut_hip_last_error())
+        bad = np.flatnonzero(out.cpu().numpy() != expect)
+        assert bad.size == 0, ("residue", r, "first difference at", int(bad[0]), "offsets", offs)
+
+
 def encode_batch(L, imgs, pitch_kind, src_shift, out_mod, ppm):
     """imgs: list of (h, w, c) arrays, or (w, h, c) tuples for shapes that must be refused"""
     n = len(imgs)
@@ -184,6 +211,25 @@ def test_encode_matrix(L, comp, pitch_kind):
             expect[offs[k]:offs[k] + len(f)] = np.frombuffer(f, np.uint8)
         bad = np.flatnonzero(got != expect)
         assert bad.size == 0, (src_shift, out_mod, "first difference at", int(bad[0]), [k for k in range(len(offs)) if offs[k] <= bad[0]][-1:])
+
+
+def test_encode_runs_at_every_output_alignment(L):
+    """rgb8 images of 1 and 5 pixels by 2 rows (bodies of 8 and 32 bytes behind the 122-byte header), each file at every residue
+    modulo 16 in turn: 16 launches, the whole allocation with its 0xA5 fill against the reference's files"""
+    rng = np.random.default_rng(77)
+    imgs = [rng.integers(0, 256, (2, w, 3), dtype=np.uint8) for w in (1, 5)]
+    want = [np.frombuffer(bmp_ref_c.write(im, 0, 0), np.uint8) for im in imgs]
+    seen = [set(), set()]
+    for r in range(16):
+        rc, st, olen, got, offs = encode_batch(L, imgs, "tight", 0, r, 0)
+        assert rc == 0 and st == [0, 0] and olen == [f.size for f in want]
+        expect = np.full(got.size, 0xA5, np.uint8)
+        for k, f in enumerate(want):
+            expect[offs[k]:offs[k] + f.size] = f
+            seen[k].add(offs[k] % 16)
+        bad = np.flatnonzero(got != expect)
+        assert bad.size == 0, ("residue", r, "first difference at", int(bad[0]), "offsets", offs)
+    assert seen == [set(range(16))] * 2
 
 
 def test_round_trip_on_the_device(L):

@@ -341,6 +341,63 @@ def test_no_gpu_means_loud_failure_not_fallback():
     assert (qd.width, qd.height, qd.channels) == (5, 4, 3)                 # the header was read; nothing was decoded on the CPU
 
 
+def test_every_remaining_entry_point_reports_no_device_and_touches_nothing():
+    """the entry points the other CPU tests do not pin: ERR_NO_DEVICE (NULL from a host drop-in), the message, and every output --
+    pixel buffer, per-image status, length -- exactly as the caller left it"""
+    L = _capi.lib()
+    if L.gamut_hip_device_count() > 0:
+        pytest.skip("a GPU is present")
+    CANARY = 0xA5
+    out = np.full(4096, CANARY, np.uint8)                                    # stands for the device output: never dereferenced without a device
+    src = np.arange(96 * 4, dtype=np.uint8) % 251
+    src0 = src.copy()
+    st = (C.c_int * 1)(-77)
+    n = C.c_int(-77)
+    off = (C.c_int64 * 1)(0)
+    files = {"png": open(os.path.join(G, "ref_images", "issue76.png"), "rb").read(), "jpg": open(os.path.join(G, "ref_images", "issue35.jpg"), "rb").read(),
+             "qoi": gen.qoi_encode(gen.synth_rgb(5, 4, 1))}
+    bufs = {k: np.frombuffer(v, np.uint8) for k, v in files.items()}
+    ptr = {k: (C.c_void_p * 1)(b.ctypes.data) for k, b in bufs.items()}
+    lens = {k: (C.c_size_t * 1)(b.size) for k, b in bufs.items()}
+    qsize = (C.c_int * 1)(bufs["qoi"].size)
+    qd = (_capi.QoiDesc * 1)()
+    assert L.gamut_hip_qoi_read_header(bufs["qoi"].ctypes.data, bufs["qoi"].size, qd) == _capi.OK
+    enc_desc = _capi.QoiDesc(4, 3, 4, 0)
+    idesc = (_capi.InflateDesc * 1)()
+    idesc[0].src = src.ctypes.data; idesc[0].dst = out.ctypes.data; idesc[0].src_len = 16; idesc[0].dst_cap = 64
+    words = np.full(2, 0xA5A5A5A5, np.uint32)
+    pinfo, jinfo = (_capi.PngInfo * 1)(), (_capi.JpegFrame * 1)()
+    o, s = out.ctypes.data, src.ctypes.data
+    device_entries = [
+        ("flip_device", lambda: L.gamut_hip_flip_device(O.PT["rgba8"], o, 16, 0, 4, 3, 1, 1, None)),
+        ("flip", lambda: L.gamut_hip_flip(O.PT["rgba8"], o, 16, 4, 3, 1)),
+        ("inflate_batch_device", lambda: L.gamut_hip_inflate_batch_device(idesc, 1, words.ctypes.data, words.ctypes.data + 4, None)),
+        ("inflate_batch_device_sliced", lambda: L.gamut_hip_inflate_batch_device_sliced(idesc, 1, words.ctypes.data, words.ctypes.data + 4, 4096, None)),
+        ("png_decode_batch_device", lambda: L.gamut_hip_png_decode_batch_device(ptr["png"], lens["png"], 1, 4, 8, off, o, pinfo, st, 1, None)),
+        ("qoi_decode_batch_device", lambda: L.gamut_hip_qoi_decode_batch_device(ptr["qoi"], qsize, 1, 4, off, o, qd, st, None)),
+        ("qoi_decode_resident_device", lambda: L.gamut_hip_qoi_decode_resident_device(bufs["qoi"].ctypes.data, bufs["qoi"].size, off, qsize, qd, 1, 4, off, o, None)),
+        ("jpeg_decode_batch_device", lambda: L.gamut_hip_jpeg_decode_batch_device(ptr["jpg"], lens["jpg"], 1, 4, off, o, jinfo, st, None, None)),
+    ]
+    host_drop_ins = [
+        ("qoi_encode", lambda: L.gamut_hip_qoi_encode(s, C.byref(enc_desc), 16, C.byref(n))),
+        ("jpeg_encode", lambda: L.gamut_hip_jpeg_encode(s, 4, 3, 3, 12, 90, C.byref(n))),
+        ("png_write_to_mem", lambda: L.gamut_hip_png_write_to_mem(s, 16, 4, 3, 4, C.byref(n), 0, -1, 5)),
+        ("bmp_write_to_mem", lambda: L.gamut_hip_bmp_write_to_mem(s, 16, 4, 3, 4, 0, 0, C.byref(n))),
+        ("gif_write_to_mem", lambda: L.gamut_hip_gif_write_to_mem(s, 16, 48, 4, 3, 2, 7, 16, 10, C.byref(n))),
+    ]
+    for name, call in device_entries + host_drop_ins:
+        L.gamut_hip_scanlines_convert_device(-1, o, 4, 0, 12, o, 4, 0, 1, 1, 1, None)      # leaves another message behind
+        assert b"no HIP device" not in L.gamut_hip_last_error()
+        rc = call()
+        if (name, call) in host_drop_ins:
+            assert not rc, name
+        else:
+            assert rc == _capi.ERR_NO_DEVICE, name
+        assert b"no HIP device" in L.gamut_hip_last_error(), name
+        assert (out == CANARY).all() and (words == 0xA5A5A5A5).all() and st[0] == -77 and n.value == -77, name
+        assert np.array_equal(src, src0), name
+
+
 def test_argument_validation_needs_no_device():
     L = _capi.lib()
     d = np.zeros(64, np.uint8)

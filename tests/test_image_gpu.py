@@ -324,3 +324,89 @@ def test_concurrent_host_threads(hip):
     for t in threads: t.start()
     for t in threads: t.join()
     assert not errors, errors[:3]
+
+
+def _encode_one_on_device(hip, fmt, px):
+    """px (layers, h, w, c) uint8 -> the bytes that format's own *_encode_batch_device makes of it in a batch of one (tight rows in HBM)"""
+    import ctypes as C
+    layers, h, w, c = px.shape
+    flat = np.ascontiguousarray(px).reshape(-1)
+    src = hip.gamut_hip_device_malloc(flat.size)
+    assert src
+    _capi.check(hip.gamut_hip_memcpy_h2d(src, flat.ctypes.data, flat.size, None))
+    i32 = lambda v: (C.c_int32 * 1)(v)
+    i64 = lambda v: (C.c_int64 * 1)(v)
+    ptr, pitch, off, n, st = (C.c_void_p * 1)(src), i64(w * c), i64(0), i64(-1), (C.c_int * 1)(77)
+    if fmt == "qoi":
+        desc = (_capi.QoiDesc * 1)(_capi.QoiDesc(w, h, c, 0))
+        bound = hip.gamut_hip_qoi_encode_bound(desc)
+        call = lambda out: hip.gamut_hip_qoi_encode_batch_device(ptr, pitch, desc, 1, off, out, n, st, None)
+    elif fmt == "jpeg":
+        bound = hip.gamut_hip_jpeg_encode_bound(w, h, c, 90)
+        call = lambda out: hip.gamut_hip_jpeg_encode_batch_device(ptr, pitch, i32(w), i32(h), i32(c), i32(90), 1, off, out, n, st, None)
+    elif fmt == "png":                                                       # savePNG's defaults: filters selected, ENCODE_PNG_COMPRESSION_5 - 1
+        bound = hip.gamut_hip_png_encode_bound(w, h, c, 0)
+        call = lambda out: hip.gamut_hip_png_encode_batch_device(ptr, pitch, i32(w), i32(h), i32(c), i32(0), i32(-1), i32(gi.ENCODE_PNG_COMPRESSION_5 - 1), 1,
+                                                                 off, out, n, st, None)
+    elif fmt == "bmp":
+        bound = hip.gamut_hip_bmp_encode_bound(w, h, c)
+        call = lambda out: hip.gamut_hip_bmp_encode_batch_device(ptr, pitch, i32(w), i32(h), i32(c), i32(0), i32(0), 1, off, out, n, st, None)
+    else:
+        bound = hip.gamut_hip_gif_encode_bound(w, h, layers)
+        call = lambda out: hip.gamut_hip_gif_encode_batch_device(ptr, pitch, i64(h * w * c), i32(w), i32(h), i32(layers), None, None, None, 1, off, out, n, st, None)
+    assert bound > 0
+    out = hip.gamut_hip_device_malloc(bound)
+    assert out
+    try:
+        _capi.check(call(out))
+        assert st[0] == 0 and 0 < n[0] <= bound
+        data = np.zeros(n[0], np.uint8)
+        _capi.check(hip.gamut_hip_memcpy_d2h(data.ctypes.data, out, data.size, None))
+        _capi.check(hip.gamut_hip_stream_synchronize(None))
+        return data.tobytes()
+    finally:
+        hip.gamut_hip_device_free(out); hip.gamut_hip_device_free(src)
+
+
+def test_saves_of_every_format_share_one_staging(hip):
+    """One thread saves PNG, BMP, GIF, QOI, JPEG and PNG again, then a larger PNG: the single-image encodes of all codecs stage through
+    one pair of per-thread buffers, so the sizes grow, shrink (the buffers are used below their capacity) and grow past it (the
+    outgrown buffers are parked and new ones made).  Host images first, then device images; every file equals what its format's
+    batch entry makes of the same pixels in a batch of one, and the host image's bytes equal the device image's."""
+    rng = np.random.default_rng(61)
+    def smooth(layers, h, w, c):                                             # gradients with a little noise: every codec has something to compress
+        y, x = np.mgrid[0:h, 0:w]
+        base = (x * 3 + y * 5)[None, :, :, None] + np.arange(layers)[:, None, None, None] * 40 + np.arange(c)[None, None, None, :] * 17
+        return ((base + rng.integers(0, 4, (layers, h, w, c))) % 256).astype(np.uint8)
+    steps = [("png", smooth(1, 80, 96, 4)), ("bmp", smooth(1, 3, 5, 3)), ("gif", smooth(2, 5, 9, 4)), ("qoi", smooth(1, 7, 33, 3)),
+             ("jpeg", smooth(1, 9, 17, 3))]
+    steps += [steps[0], ("png", smooth(1, 120, 160, 4))]
+    want = [_encode_one_on_device(hip, fmt, px) for fmt, px in steps]         # computed once, before either pass
+    TYPE = {3: PT["rgb8"], 4: PT["rgba8"]}
+
+    def save(im, fmt):
+        if fmt == "png": return im.save_png_to_memory()
+        if fmt == "bmp": return im.save_bmp_to_memory()
+        return im.save_to_memory({"gif": gi.FORMAT_GIF, "qoi": gi.FORMAT_QOI, "jpeg": gi.FORMAT_JPEG}[fmt])
+
+    got = {False: [], True: []}
+    for device in (False, True):
+        for fmt, px in steps:
+            layers, h, w, c = px.shape
+            im = Image(device=device)
+            if device:
+                assert im.createLayered(w, h, layers, TYPE[c], 0)
+                for l in range(layers):
+                    for y in range(h):
+                        _capi.check(hip.gamut_hip_memcpy_h2d(im.layerptr(l, y), px[l, y].ctypes.data, w * c, None))
+                _capi.check(hip.gamut_hip_stream_synchronize(None))
+            else:
+                assert im.createLayeredView(px.reshape(-1), w, h, layers, TYPE[c], w * c, h * w * c)
+            data = save(im, fmt)
+            assert data is not None, (fmt, device, _capi.last_error())
+            got[device].append(data)
+    for k, (fmt, px) in enumerate(steps):
+        assert got[False][k] == want[k], ("host image", k, fmt, px.shape)
+        assert got[True][k] == want[k], ("device image", k, fmt, px.shape)
+        assert got[False][k] == got[True][k]
+    assert got[False][0] == got[False][5]

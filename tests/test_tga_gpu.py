@@ -91,6 +91,34 @@ def check_batch(L, files, req, names=None):
 VARIANTS = tga_cases.variant_files()
 
 
+def test_unpacked_runs_at_every_output_alignment(L):
+    """a row of 1 pixel (3 bytes: shorter than the 16-byte head of its store), of 5 (head and tail, no 16-byte body) and of 1025 (one
+    pixel into a second 1024-pixel unit) in one batch of three 2-row true-colour files at req_comp 3, with EVERY out_offset at
+    residue r modulo 16, r = 0..15 in turn; the whole allocation, canaries included, against the Python reading of the reference"""
+    import tga_ref
+    files = [tga_gen.make(w, 2, 2, 24, top_down=w == 5, seed=w) for w in (1, 5, 1025)]
+    refs = [tga_ref.decode(f, 3)[0] for f in files]
+    assert [r.shape for r in refs] == [(2, 1, 3), (2, 5, 3), (2, 1025, 3)]
+    bufs = [np.frombuffer(f, np.uint8) for f in files]
+    ptrs = (C.c_void_p * 3)(*[b.ctypes.data for b in bufs]); lens = (C.c_size_t * 3)(*[b.size for b in bufs])
+    for r in range(16):
+        offs, pos = [], 0
+        for ref in refs:
+            pos = (pos + 64 + 15) // 16 * 16 + r                            # at least 64 canary bytes in front of every image
+            offs.append(pos); pos += ref.size
+        pos += 64
+        expect = np.full(pos, 0xA5, np.uint8)
+        for ref, o in zip(refs, offs):
+            expect[o:o + ref.size] = ref.reshape(-1)
+        out = torch.full((pos,), 0xA5, dtype=torch.uint8, device="cuda")
+        assert out.data_ptr() % 16 == 0 and all(o % 16 == r for o in offs)
+        info = (_capi.TgaInfo * 3)(); st = (C.c_int * 3)(77, 77, 77)
+        rc = L.gamut_hip_tga_decode_batch_device(ptrs, lens, 3, 3, (C.c_int64 * 3)(*offs), out.data_ptr(), info, st, None)
+        assert rc == 0 and list(st) == [0, 0, 0], (r, L.gamut_hip_last_error())
+        bad = np.flatnonzero(out.cpu().numpy() != expect)
+        assert bad.size == 0, ("residue", r, "first difference at", int(bad[0]), "offsets", offs)
+
+
 @pytest.mark.parametrize("req", [0, 3, 4])
 def test_every_variant_and_geometry_in_one_call(L, req):
     """types 1 / 2 / 3 / 9 / 10 / 11 x every depth and colour-map entry size x 8- and 16-bit indices at 1x1, 3x2, 5x3, 33x5, 257x7 and
