@@ -211,7 +211,7 @@ extern "C" int gamut_hip_decode_batch_device(const uint8_t* const* data, const s
         };
         // The longest legs first on the workers (PNG: inflate-bound, QOI: PCIe-bound), JPEG on the calling thread.  When another
         // thread's mixed batch holds the workers, the legs run one after the other here: same results.
-        static const bool serial = [] { const char* e = getenv("GAMUT_HIP_MIXED_SERIAL"); return e && *e && atoi(e) != 0; }();     // measurements
+        static const bool serial = env_flag("GAMUT_HIP_MIXED_SERIAL");     // measurements
         Pool& P = pool(dev);
         const int legs = (int)!idx[0].empty() + (int)!idx[1].empty() + (int)!idx[2].empty();
         if (legs > 1 && !serial && P.busy.try_lock()) {

@@ -36,6 +36,7 @@ bool have_device();
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool env_flag(const char* name) { const char* e = getenv(name); return e && *e && atoi(e) != 0; }      // GAMUT_HIP_*_TIMING=1
+inline int env_int(const char* name, int fallback) { const char* e = getenv(name); return e && *e ? atoi(e) : fallback; }      // the read-once integer knobs (measurements)
 
 // A host process may drive several GPUs from one thread (hipSetDevice between calls) -- what a D host with "one host thread +
 // one HIP stream per GPU"  does as well as a thread that simply serves two devices in turn.  Everything the

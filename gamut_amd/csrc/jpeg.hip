@@ -45,7 +45,7 @@ struct JpegArgs {
     int scan_type, out_comps;
     int count;                                       // images of this launch
     // the compact hand-off (k_jpeg_h2v2<.., TOK>): instead of `coeffs`, image i's coefficients are the tokens
-    // tokens[tok_offs[i] + strip_tab[strip_offs[i] + s] .. strip_tab[strip_offs[i] + s + 1]) of strip s (jpeg_host.hip, SUB_TOKENS)
+    // tokens[tok_offs[i] + strip_tab[strip_offs[i] + s] .. strip_tab[strip_offs[i] + s + 1]) of strip s (jpeg_entropy_kernels.hpp, SUB_TOKENS)
     const u32* tokens; const u32* strip_tab; const int64_t* tok_offs; const int64_t* strip_offs;
     int nt;                                          // every row of every image starts on a 128-byte line (the launcher's verdict): the packed outputs' 16-byte chunks leave
                                                      // with the nontemporal hint (rgb8 2.81 -> 2.78 ms, l8 2.64 -> 2.62; off the lines the hint costs 15 %: profiles/r06_jpeg_packed_nt_ab.txt)
@@ -1072,8 +1072,8 @@ int jpeg_reconstruct_launch(const int16_t* coeffs, int64_t coeff_stride,
     return GAMUT_HIP_OK;
 }
 
-// 4:2:0 images whose coefficients arrive as token streams (the compact hand-off of gamut_hip_jpeg_decode_batch_device: jpeg_host.hip,
-// SUB_TOKENS): same kernel, the strip's tile assembled in LDS from its tokens.  tok_offs / strip_offs: per-image offsets (device arrays).
+// 4:2:0 images whose coefficients arrive as token streams (the compact hand-off of gamut_hip_jpeg_decode_batch_device: jpeg_host.hip;
+// the tokens: jpeg_entropy_kernels.hpp, SUB_TOKENS): same kernel, the strip's tile assembled in LDS from its tokens.  tok_offs / strip_offs: per-image offsets (device arrays).
 int jpeg_reconstruct_tokens_launch(const uint32_t* tokens, const uint32_t* strip_tab, const int64_t* tok_offs, const int64_t* strip_offs,
                                    const uint8_t* max_zag, int64_t zag_stride, uint8_t* out, int64_t out_pitch, int64_t out_stride,
                                    int width, int height, int out_comps, int count, hipStream_t stream)

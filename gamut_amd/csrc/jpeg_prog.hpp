@@ -1,5 +1,6 @@
-// jpeg_prog.hpp -- progressive (SOF2) entropy decode ON THE GPU.  Included by jpeg_host.hip inside its namespace (it shares the
-// marker parser, the Huffman table forms and the bit reader with the baseline device decoder).
+// jpeg_prog.hpp -- progressive (SOF2) entropy decode ON THE GPU.  Included by jpeg_host.hip inside its namespace, behind
+// jpeg_parse.hpp (the marker parser, the host feeder that is its oracle), jpeg_entropy_kernels.hpp (DevHuff, the bit reader) and
+// jpeg_batch.hpp (the marker walk of the unstuffers, host_redo, the stream guard and the small batch helpers).
 //
 // A progressive file is a sequence of scans (jpegload.d:3296-3664): DC first / DC refinement (all components, coefficient 0)
 // and, per component, AC first / AC refinement scans over a band [Ss, Se] of the zig-zag order, each refining the bits the
@@ -750,67 +751,32 @@ void prog_prepare(int i, const uint8_t* base, size_t n, gamut_hip_jpeg_frame& f,
 }
 
 // the scans of one file, unstuffed and cut at the restart markers, into the file's slot of the pinned upload image
-void prog_unstuff(int i, const uint8_t* base, gamut_hip_jpeg_frame& f, ProgPrep& out, uint8_t* dst)
+void prog_unstuff(int i, const uint8_t* base, ProgPrep& out, uint8_t* dst)
 {
     size_t w = 0;
     bool bad = false;
-    for (size_t si = 0; si < out.scans.size(); ++si) {
+    for (size_t si = 0; si < out.scans.size() && !bad; ++si) {
         const ProgScanPrep& s = out.scans[si];
-        const int total = s.units, ri = s.restart_interval;
-        int next_unit = 0, expect = 0, n_seg = 0;
-        size_t q = s.begin, copy_from = s.begin, seg_begin = w;
-        const size_t n = s.end;
-        bool copying = true;
-        auto flush = [&](size_t upto) {
-            if (copying && upto > copy_from) {
-                const size_t k = upto - copy_from;
-                if (w + k > out.cap) { bad = true; return; }
-                memcpy(dst + w, base + copy_from, k); w += k;
-            }
-        };
-        int fill = 0;                                          // 0xFF bytes in front of the marker under way, besides its own
-        auto close_segment = [&](int nu, int tail) {
-            if (w + 64 + 16 > out.cap) { bad = true; return; }
-            ProgItem it; memset(&it, 0, sizeof(it));
-            it.image = i; it.kind = s.kind; it.ncomp = s.sc.ncomp; it.ss = s.sc.ss; it.se = s.sc.se; it.al = s.sc.al;
-            for (int k = 0; k < s.sc.ncomp; ++k) { it.comp[k] = s.sc.comp[k]; it.tab[k] = s.tab[k]; }
-            it.first_unit = next_unit; it.n_units = nu; it.nbx = s.nbx > 0 ? s.nbx : 1; it.level = s.level;
-            it.begin = seg_begin; it.end = w;
-            it.scan = (int32_t)si; it.seg = n_seg++; it.tail = tail;
-            it.dep[0] = it.dep[1] = it.dep[2] = -1;
-            out.items.push_back(it); next_unit += nu;
-            memset(dst + w, 0xFF, 64); w += 64;
-            w = (w + 3) & ~(size_t)3;                          // segments start on dword boundaries (the wave reader loads dwords)
-            seg_begin = w;
-        };
-        while (!bad) {
-            const uint8_t* hit = q < n ? (const uint8_t*)memchr(base + q, 0xFF, n - q) : nullptr;
-            if (!hit || hit + 1 >= base + n) { flush(n); q = n; break; }
-            const uint8_t m = hit[1];
-            q = (size_t)(hit - base);
-            if (m == 0x00) {
-                if (!copying) { bad = true; break; }                                    // FF .. FF 00: the input stopped at the first FF (see unstuff_file)
-                flush(q + 1); copy_from = q + 2; q += 2; continue;                      // stuffed 0xFF: keep the FF, drop the 00
-            }
-            flush(q); copying = false;
-            if (m == 0xFF) { q += 1; fill = std::min(fill + 1, 4096); continue; }
-            if (m >= 0xD0 && m <= 0xD7 && ri && next_unit + ri < total) {
-                if (m != 0xD0 + expect) { bad = true; break; }
-                close_segment(ri, fill); fill = 0;
-                expect = (expect + 1) & 7; q += 2; copy_from = q; copying = true;
-                continue;
-            }
-            break;
-        }
-        if (!bad && q < n) bad = true;                         // an RSTn the scan has no use for: the reference's input stops THERE, prog_prepare looked for the next scan behind it
-        if (!bad && next_unit < total) {
-            if (ri && total - next_unit > ri) bad = true;      // a restart marker is missing
-            else close_segment(total - next_unit, -1);
-        }
-        if (bad) break;
+        int n_seg = 0;
+        size_t q = 0;
+        // (s.end is where prog_prepare found the next scan: an RSTn the scan has no use for in front of it is where the reference's input stops)
+        bad = !unstuff_scan(base, s.begin, s.end, s.restart_interval, s.units, true, dst, out.cap, w, q,
+            [&](int first_unit, int n_units, size_t seg_begin, int tail) {
+                if (w + 64 + 16 > out.cap) return false;
+                ProgItem it; memset(&it, 0, sizeof(it));
+                it.image = i; it.kind = s.kind; it.ncomp = s.sc.ncomp; it.ss = s.sc.ss; it.se = s.sc.se; it.al = s.sc.al;
+                for (int k = 0; k < s.sc.ncomp; ++k) { it.comp[k] = s.sc.comp[k]; it.tab[k] = s.tab[k]; }
+                it.first_unit = first_unit; it.n_units = n_units; it.nbx = s.nbx > 0 ? s.nbx : 1; it.level = s.level;
+                it.begin = seg_begin; it.end = w;
+                it.scan = (int32_t)si; it.seg = n_seg++; it.tail = tail;
+                it.dep[0] = it.dep[1] = it.dep[2] = -1;
+                out.items.push_back(it);
+                memset(dst + w, 0xFF, 64); w += 64;
+                w = (w + 3) & ~(size_t)3;                      // segments start on dword boundaries (the wave reader loads dwords)
+                return true;
+            });
     }
     out.used = w;
-    (void)f;
     if (bad) { out.items.clear(); out.used = 0; out.rc = kHostRedo; }       // what the reference makes of such a restart structure is the host feeder's to say
 }
 
@@ -822,15 +788,12 @@ int progressive_decode_device(const uint8_t* const* data, const size_t* len, con
                               int16_t* d_coeffs, uint8_t* d_max_zag, uint32_t* d_status,
                               gamut_hip_jpeg_frame* info, int* host_status, hipStream_t stream, int* first_index, char* first_msg, size_t msg_cap)
 {
-    const bool trace = getenv("GAMUT_HIP_TRACE") != nullptr;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    const bool trace = trace_enabled();
+    const TracePoint t_begin = trace_now();
     const int n = (int)idx.size();
     *first_index = -1;
     if (n == 0) return GAMUT_HIP_OK;
-    int workers = host_threads();
-    workers = workers < 1 ? 1 : workers > 16 ? 16 : workers;
-    if (workers > n) workers = n;
+    const int workers = batch_workers(n);
     // A scan is a chain: the GPU decodes a 1080p file's longest one in 63 ms (round 4; whatever the batch, up to a few hundred files) where a
     // host core needs 20 ms for the whole file, and wins by decoding every scan of every file at the same time.  Below five files per host
     // thread the host feeder (Progressive::run on the thread pool) plus an upload of the coefficients is the faster way to the same buffers
@@ -857,10 +820,8 @@ int progressive_decode_device(const uint8_t* const* data, const size_t* len, con
     }
     std::vector<ProgPrep> prep((size_t)n);
     {
-        std::vector<Parser*> parsers((size_t)workers, nullptr);
-        for (Parser*& p : parsers) p = new Parser();
-        parallel_for(n, workers, [&](int w, int k) { const int i = idx[(size_t)k]; prog_prepare(i, data[i], len[i], info[i], prep[(size_t)k], *parsers[(size_t)w]); });
-        for (Parser* p : parsers) delete p;
+        ParserPool parsers(workers);
+        parallel_for(n, workers, [&](int w, int k) { const int i = idx[(size_t)k]; prog_prepare(i, data[i], len[i], info[i], prep[(size_t)k], parsers[w]); });
     }
     // layout: blob slots, global tables
     std::vector<ProgImage> images((size_t)n);
@@ -882,7 +843,7 @@ int progressive_decode_device(const uint8_t* const* data, const size_t* len, con
         for (const ProgScanPrep& s : pp.scans) if (s.level > max_level) max_level = s.level;
         if (im.n_blocks > max_blocks) max_blocks = im.n_blocks;
         blob_off[(size_t)k] = blob_size;
-        blob_size += (pp.cap + 255) & ~(size_t)255;
+        blob_size += up256(pp.cap);
     }
     const double ms_parse = ms_since(t_begin);
     double ms_unstuff = 0, ms_kernels = 0;
@@ -894,10 +855,11 @@ int progressive_decode_device(const uint8_t* const* data, const size_t* len, con
         uint8_t* d_blob = (uint8_t*)scratch.get(blob_size + kBlobSlack, stream);
         uint8_t* h_blob = pinned.get(blob_size + kBlobSlack, stream);
         if (!d_blob || !h_blob) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "jpeg: staging allocation of %zu bytes failed", blob_size + kBlobSlack);
-        const auto t_u = std::chrono::steady_clock::now();
+        StreamDrain drain; drain.arm(stream);                  // the staging is the thread's: every way out from here on waits for `stream`
+        const TracePoint t_u = trace_now();
         parallel_for(n, workers, [&](int, int k) {
             ProgPrep& pp = prep[(size_t)k];
-            if (pp.rc == GAMUT_HIP_OK) { const int i = idx[(size_t)k]; prog_unstuff(i, data[i], info[i], pp, h_blob + blob_off[(size_t)k]); }
+            if (pp.rc == GAMUT_HIP_OK) { const int i = idx[(size_t)k]; prog_unstuff(i, data[i], pp, h_blob + blob_off[(size_t)k]); }
         });
         memset(h_blob + blob_size, 0xFF, kBlobSlack);
         // the coefficient blocks of the images start at zero (scans only write what they decode); adjacent images in one call
@@ -1018,12 +980,11 @@ int progressive_decode_device(const uint8_t* const* data, const size_t* len, con
         }
         ms_unstuff = ms_since(t_u);
         if (!live.empty()) {
-            auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
             const size_t n_items = all_items.size();
             std::vector<QuantTab>& qn = quants;
-            const size_t o_img = 0, o_huff = align(live.size() * sizeof(ProgImage)), o_quant = align(o_huff + huffs.size() * sizeof(DevHuff)),
-                         o_items = align(o_quant + qn.size() * sizeof(QuantTab)), o_prog = align(o_items + n_items * sizeof(ProgItem)),
-                         o_times = align(o_prog + (n_items + 1 + live.size()) * sizeof(uint32_t)), total = o_times + (trace ? 2 * n_items * sizeof(uint4) : 0) + 256;
+            const size_t o_img = 0, o_huff = up256(live.size() * sizeof(ProgImage)), o_quant = up256(o_huff + huffs.size() * sizeof(DevHuff)),
+                         o_items = up256(o_quant + qn.size() * sizeof(QuantTab)), o_prog = up256(o_items + n_items * sizeof(ProgItem)),
+                         o_times = up256(o_prog + (n_items + 1 + live.size()) * sizeof(uint32_t)), total = o_times + (trace ? 2 * n_items * sizeof(uint4) : 0) + 256;
             uint8_t* d = (uint8_t*)tab_scratch.get(total, stream);
             uint8_t* h = tab_pinned.get(total, stream);
             if (!d || !h) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "jpeg: staging allocation of %zu bytes failed", total);
@@ -1043,14 +1004,14 @@ int progressive_decode_device(const uint8_t* const* data, const size_t* len, con
                 if (!st) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "jpeg: status allocation failed");
             }
             for (int k = 0; k < n; ++k) if (prep[(size_t)k].rc == GAMUT_HIP_OK) GAMUT_HIP_CHECK(hipMemsetAsync(st + idx[(size_t)k], 0, sizeof(uint32_t), stream));
-            const auto t_k = std::chrono::steady_clock::now();
+            const TracePoint t_k = trace_now();
             if (n_items) {
                 hipLaunchKernelGGL(k_prog_scan, dim3((unsigned)n_items), dim3(kProgThreads), 0, stream,
                                    (const ProgItem*)(d + o_items), (const ProgImage*)(d + o_img), (const DevHuff*)(d + o_huff), d_blob, d_coeffs, st,
                                    (uint32_t*)(d + o_prog), (uint32_t*)(d + o_prog) + n_items, trace ? (uint4*)(d + o_times) : (uint4*)nullptr);
                 if (int rc = launch_status("jpeg_prog_scan")) return rc;
                 if (trace) {
-                    const auto t_l = std::chrono::steady_clock::now();
+                    const TracePoint t_l = trace_now();
                     (void)hipStreamSynchronize(stream);
                     fprintf(stderr, "[gamut_hip]   scans: %zu segments in one launch, %.1f ms (with what was queued before it)\n", n_items, ms_since(t_l));
                     std::vector<uint4> tm(2 * n_items);
@@ -1083,7 +1044,7 @@ int progressive_decode_device(const uint8_t* const* data, const size_t* len, con
             hipLaunchKernelGGL(k_prog_finalize, dim3(gx, (unsigned)live.size()), dim3(256), 0, stream,
                                (const ProgImage*)(d + o_img), (int)live.size(), (const int16_t*)(d + o_quant), d_coeffs, d_max_zag);
             if (int rc = launch_status("jpeg_prog_finalize")) return rc;
-            GAMUT_HIP_CHECK(hipStreamSynchronize(stream));     // the per-thread staging buffers are reused by the next call
+            GAMUT_HIP_CHECK(drain.wait());                     // the per-thread staging buffers are reused by the next call
             // whatever a kernel flagged -- a bit pattern no code word begins, a run past coefficient 63, a segment that ran out, octets between an
             // interval's last bit and its RSTn (restart_leftover_bad) -- is the host feeder's to judge (kHostRedo, below)
             {

@@ -1655,7 +1655,7 @@ int png_defilter_launch(const uint8_t* raw, int64_t raw_stride, uint32_t raw_len
         // group: images whose bands are dealt out side by side (band-major inside a group).  The whole batch: band b + 1 of an image is
         // then drawn count draws after band b, by when band b has the ~90 trips of head start band b + 1 needs (groups of 128 of
         // 512 4K images: waves queue up behind their producers, -25 %).  GAMUT_HIP_PNG_GROUP overrides (measurements).
-        static const int group_env = [] { const char* e = getenv("GAMUT_HIP_PNG_GROUP"); return e && *e ? atoi(e) : 0; }();      // (read once: not a getenv per launch)
+        static const int group_env = env_int("GAMUT_HIP_PNG_GROUP", 0);      // (read once: not a getenv per launch)
         const u32 group = group_env > 0 ? (u32)group_env : (u32)count;
         const u32 ngroups = ((u32)count + group - 1) / group;
         a.group = ((u32)count + ngroups - 1) / ngroups;              // equal groups

@@ -223,7 +223,7 @@ def describe_difference(c, got, exp):
 
 # ------------------------------------------------------------------------------------------------ the token cases
 TOKEN_SIZES = ((128, 40), (133, 40))
-TOKEN_MIN_SCAN = 4096            # jpeg_host.hip, kSyncMinBytes: a shorter scan takes one lane and keeps the dense blocks
+TOKEN_MIN_SCAN = 4096            # jpeg_entropy_kernels.hpp, kSyncMinBytes: a shorter scan takes one lane and keeps the dense blocks
 TOKEN_OFFSETS = ("lines", "off4", "irregular")
 
 

@@ -115,7 +115,7 @@ def test_the_images_of_a_batch_differ_and_max_zag_shows(scan_type):
 
 
 def test_the_token_files_are_distinct_and_long_enough_for_tokens():
-    """17 distinct files per size whose pixels differ pairwise, each with a scan of at least kSyncMinBytes (jpeg_host.hip): shorter scans keep the dense blocks
+    """17 distinct files per size whose pixels differ pairwise, each with a scan of at least kSyncMinBytes (jpeg_entropy_kernels.hpp): shorter scans keep the dense blocks
     whatever GAMUT_HIP_JPEG_HANDOFF says"""
     for (w, h) in B.TOKEN_SIZES:
         blobs = B.token_files(w, h)

@@ -160,3 +160,109 @@ def test_file_batches_every_token_variant(hip, handoff):
                     k = int(np.flatnonzero(got != exp)[0])
                     failures.append(f"{where}: allocation byte {k - G} (image slots start at {offs[:4].tolist()} ...): got {got[k:k + 8].tolist()} want {exp[k:k + 8].tolist()}")
     assert not failures, f"{len(failures)} differences:\n" + "\n".join(failures[:8])
+
+
+def _dc_category_16(blob):
+    """the file with the value 11 of its first DC table -- a category only a DC difference of 1024 or more uses: none in smooth content -- replaced by 16: the
+    same image, but a table the kernels are not given (the host feeder decodes the file behind the device pass)"""
+    out = bytearray(blob)
+    p = 2
+    while out[p + 1] != 0xDA:
+        n = (out[p + 2] << 8) | out[p + 3]
+        if out[p + 1] == 0xC4:
+            q = p + 4
+            while q < p + 2 + n:
+                count = sum(out[q + 1:q + 17])
+                if out[q] >> 4 == 0:
+                    k = out.index(11, q + 17, q + 17 + count)
+                    out[k] = 16
+                    return bytes(out)
+                q += 17 + count
+        p += 2 + n
+    raise AssertionError("no DC table")
+
+
+def _stage_files():
+    """one small file of every class the batch call tells apart -> [(name, bytes)]; the classes are checked below through gamut_hip_jpeg_scan_layout"""
+    import io
+    from PIL import Image
+    import gen
+    rng = np.random.default_rng(77)
+
+    def jpeg(px, **kw):
+        bio = io.BytesIO(); Image.fromarray(px).save(bio, "JPEG", **kw)
+        return bio.getvalue()
+    smooth = gen.synth_rgb(96, 64, 5)
+    return [("420 long", B.token_files(128, 40)[0]),
+            ("444 long", jpeg(rng.integers(0, 256, (64, 64, 3), dtype=np.uint8), quality=95, subsampling=0)),
+            ("restart short", jpeg(smooth, quality=90, subsampling=2, restart_marker_blocks=2)),
+            ("restart long", jpeg(rng.integers(0, 256, (64, 128, 3), dtype=np.uint8), quality=95, subsampling=2, restart_marker_rows=1)),
+            ("dc category 16", _dc_category_16(jpeg(smooth, quality=90, subsampling=0))),
+            ("progressive", jpeg(gen.synth_rgb(67, 45, 6), quality=85, subsampling=2, progressive=True)),
+            ("broken header", jpeg(smooth, quality=90)[:150])]
+
+
+def test_one_batch_of_every_class_across_two_groups(hip):
+    """ONE gamut_hip_jpeg_decode_batch_device call over 133 files -- 19 repeats, interleaved, of the seven files of _stage_files: two groups of files, the second
+    on a side stream -- with one file of every class the call tells apart: 4:2:0 with one scan of >= 4096 bytes (tokens), 4:4:4 with one of >= 4096 bytes
+    (dense, a workgroup), restart intervals of a few dozen bytes (unstuffed on the host, a lane each), restart intervals of >= 1024 bytes (unstuffed on
+    the device), a DC table with category 16 (the host feeder's, behind the device pass), a progressive file, a file that ends in its headers.  Every decodable
+    image == the oracle's, status_host and the return code are what the oracle's verdicts give, every byte of the allocation outside the images (gaps, the
+    slots of the files that fail, a guard on both sides) is untouched -- and the same call, made again on the same thread right after a smaller batch of
+    other files, gives the same bytes (the thread's staging is reused)."""
+    kinds = _stage_files()
+    layout = {}
+    for name, blob in kinds:
+        buf = np.frombuffer(blob, np.uint8)
+        fr = _capi.JpegFrame(); seg = C.c_int32(); nbytes = C.c_uint64()
+        rc = hip.gamut_hip_jpeg_scan_layout(buf.ctypes.data, buf.size, C.byref(fr), C.byref(seg), C.byref(nbytes))
+        layout[name] = (rc, seg.value, nbytes.value, fr.scan_type)
+    assert layout["420 long"][0] == 0 and layout["420 long"][1] == 1 and layout["420 long"][2] - 64 >= 4096 and layout["420 long"][3] == O.JPGD_YH2V2
+    assert layout["444 long"][0] == 0 and layout["444 long"][1] == 1 and layout["444 long"][2] - 64 >= 4096 and layout["444 long"][3] == O.JPGD_YH1V1
+    rc, segs, nb, _ = layout["restart short"]
+    assert rc == 0 and segs > 1 and len(dict(kinds)["restart short"]) < 1024 * segs
+    rc, segs, nb, _ = layout["restart long"]
+    assert rc == 0 and segs > 1 and nb - 64 * segs >= 1024 * segs
+    assert layout["dc category 16"][0] != 0                   # no segments for the kernels: the header walk leaves the file to the host feeder ...
+    want = [O.decompress_jpeg(blob, 4) for _, blob in kinds]
+    assert [w is not None for w in want] == [True, True, True, True, True, True, False]           # ... which decodes it, like the oracle
+
+    def call(order):
+        """-> (rc, status_host, the whole allocation, the expected allocation)"""
+        n = len(order)
+        blobs = [kinds[k][1] for k in order]
+        bufs = [np.frombuffer(b, np.uint8) for b in blobs]
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        lens = (C.c_size_t * n)(*[len(b) for b in blobs])
+        size = [want[k][0].size if want[k] is not None else 96 for k in order]              # (a slot for the files that fail too: it stays as it is)
+        steps = [(s + 127) // 128 * 128 + 128 * (i % 3) for i, s in enumerate(size)]
+        offs = np.concatenate([[0], np.cumsum(steps)[:-1]]).astype(np.int64)
+        total = 2 * B.GUARD + int(sum(steps))
+        exp = np.full(total, 0xA5, np.uint8)
+        for i, k in enumerate(order):
+            if want[k] is not None:
+                exp[B.GUARD + offs[i]:B.GUARD + offs[i] + size[i]] = want[k][0].reshape(-1)
+        d_out = _DeviceBuffer(hip, total)
+        try:
+            d_out.upload(np.full(total, 0xA5, np.uint8))
+            info = (_capi.JpegFrame * n)(); hst = (C.c_int * n)()
+            rc = hip.gamut_hip_jpeg_decode_batch_device(ptrs, lens, n, 4, offs.ctypes.data_as(C.POINTER(C.c_int64)), d_out.ptr + B.GUARD, info, hst, None, None)
+            _capi.check(hip.gamut_hip_stream_synchronize(None))
+            return rc, list(hst), d_out.download(total), exp, offs
+        finally:
+            d_out.free()
+
+    order = [i % 7 for i in range(133)]
+    rc, hst, got, exp, offs = call(order)
+    for i, k in enumerate(order):
+        assert (hst[i] == 0) == (want[k] is not None), (i, kinds[k][0], hst[i])
+    assert rc == hst[6] != 0, (rc, hst[:7])                    # the return code: the verdict of the lowest-numbered file that fails
+    if not np.array_equal(got, exp):
+        at = int(np.flatnonzero(got != exp)[0]) - B.GUARD
+        i = int(np.searchsorted(offs, at, side="right")) - 1
+        raise AssertionError(f"allocation byte {at}: file {i} ({kinds[order[i]][0] if i >= 0 else 'the guard'}) at {int(offs[i])}: got {got[at + B.GUARD:at + B.GUARD + 8].tolist()}")
+    small = [5, 3, 0, 2, 6, 1, 4, 3, 2]
+    rc_s, hst_s, got_s, exp_s, _ = call(small)
+    assert rc_s != 0 and [h == 0 for h in hst_s] == [want[k] is not None for k in small] and np.array_equal(got_s, exp_s)
+    rc2, hst2, got2, _, _ = call(order)
+    assert (rc2, hst2) == (rc, hst) and np.array_equal(got2, got)
