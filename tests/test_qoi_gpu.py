@@ -9,6 +9,7 @@ import pytest
 import gen
 import oracle_lib as O
 from gamut_amd import _capi
+from qoi_cases import _arbitrary_streams
 from test_oracle_pinning import _qoi_test_images
 
 pytestmark = pytest.mark.gpu
@@ -149,41 +150,12 @@ def test_qoi_resident_streams(hip, small_batch_kernel):
     hip.gamut_hip_device_free(blob); hip.gamut_hip_device_free(out)
 
 
-def _arbitrary_streams():
-    """streams no encoder writes: random chunk bytes under a valid header (every byte sequence is a QOI op sequence) -- too short, too
-    long, op mixes that change every window's entry offset, runs across the end of the image"""
-    rng = np.random.default_rng(31)
-    out = []
-    for k in range(24):
-        w, h, ch = int(rng.integers(1, 400)), int(rng.integers(1, 60)), 3 + (k & 1)
-        need = w * h
-        nbytes = int(rng.integers(0, 3 * need + 40))
-        body = rng.integers(0, 256, nbytes, dtype=np.uint8)
-        if k % 3 == 0:
-            body[rng.random(nbytes) < 0.5] = 0xC0 | int(rng.integers(0, 62))          # many RUN ops
-        if k % 4 == 1:
-            body[rng.random(nbytes) < 0.6] &= 0x3F                                    # many INDEX ops
-        out.append(b"qoif" + w.to_bytes(4, "big") + h.to_bytes(4, "big") + bytes([ch, 0]) + body.tobytes() + bytes(7) + b"\x01")
-    # RGB, RGBA and INDEX ops close together among DIFF / LUMA ops: every combination of "the most recent op that set the colour" and "the most
-    # recent op that set alpha" inside one group of 64 ops (qoi_group_scan's three alpha cases), in densities from a few per group to most ops
-    for k in range(16):
-        w, h, ch = int(rng.integers(40, 500)), int(rng.integers(8, 50)), 3 + (k & 1)
-        nbytes = int(rng.integers(w * h, 3 * w * h))
-        body = rng.integers(0x40, 0xC0, nbytes, dtype=np.uint8)                         # DIFF and LUMA ops (a LUMA op's second byte: any of these)
-        p_rgb, p_rgba, p_idx = [(0.02, 0.0, 0.01), (0.0, 0.02, 0.02), (0.05, 0.05, 0.05), (0.3, 0.2, 0.2)][k // 4]
-        r = rng.random(nbytes)
-        body[r < p_rgb] = 0xFE
-        body[(r >= p_rgb) & (r < p_rgb + p_rgba)] = 0xFF
-        body[(r >= p_rgb + p_rgba) & (r < p_rgb + p_rgba + p_idx)] &= 0x3F
-        if k % 4 == 3:
-            body[rng.random(nbytes) < 0.03] = 0xC0 | int(rng.integers(0, 62))
-        out.append(b"qoif" + w.to_bytes(4, "big") + h.to_bytes(4, "big") + bytes([ch, 0]) + body.tobytes() + bytes(7) + b"\x01")
-    return out
-
-
 def test_qoi_arbitrary_streams(hip, small_batch_kernel):
     files = _arbitrary_streams()
-    for reps in (1, 24):                                       # 40 streams: the small-batch kernels; 960: one wave per stream
+    # 40 streams: the small-batch kernel of the fixture.  960: the host entry cuts them into launches of 256 (kGroup, qoi.hip), so these run on the
+    # small-batch kernels too -- NOT one wave per stream: k_qoi_decode<1> starts only from the resident entry with at least 768 streams, and no test
+    # sends it these streams yet.  What the 960 cover is a launch per group, each behind its own upload.
+    for reps in (1, 24):
         blobs = files * reps
         n = len(blobs)
         if reps > 1 and small_batch_kernel == "phases":
@@ -206,8 +178,11 @@ def test_qoi_arbitrary_streams(hip, small_batch_kernel):
 
 def test_qoi_large_batches(hip):
     """800 streams in one call.  From host memory (gamut_hip_qoi_decode_batch_device) the files go up in groups of 256 on a copy stream and
-    every group is decoded behind its own upload; resident in HBM (gamut_hip_qoi_decode_resident_device) >= 768 streams run one wave per
-    stream (k_qoi_decode<1>).  Same pixels as the oracle either way, rgba and rgb outputs."""
+    every group is decoded behind its own upload, by a launch of at most 256 streams: the small-batch kernels, never one wave per stream.
+    Resident in HBM (gamut_hip_qoi_decode_resident_device) the 800 are one launch, and >= 768 streams run one wave per stream
+    (k_qoi_decode<1>): the only way to that kernel, and these 16 encoder-written images are all the suite sends it -- no stream an
+    encoder would not write (tests/qoi_cases.py has them; nothing runs them on that kernel yet).  Same pixels as the oracle either way,
+    rgba and rgb outputs."""
     rng = np.random.default_rng(9)
     imgs = []
     for k in range(16):
@@ -229,7 +204,8 @@ def test_qoi_large_batches(hip):
         descs = (_capi.QoiDesc * n)(); st = (C.c_int * n)()
         host = np.empty(int(sum(nbytes)), np.uint8)
         for resident in (False, True):
-            _capi.check(hip.gamut_hip_memcpy_h2d(dout, np.full(host.size, 0x5A, np.uint8).ctypes.data, host.size, None))
+            canary = np.full(host.size, 0x5A, np.uint8)                        # (named: a temporary's memory may be gone before the copy reads it)
+            _capi.check(hip.gamut_hip_memcpy_h2d(dout, canary.ctypes.data, host.size, None))
             if not resident:
                 _capi.check(hip.gamut_hip_qoi_decode_batch_device(ptrs, sizes, n, ch, offs.ctypes.data_as(C.POINTER(C.c_int64)), dout, descs, st, None))
             else:

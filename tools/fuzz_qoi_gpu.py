@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Mutated QOI files through gamut_hip_qoi_decode_batch_device (every kernel: a batch of 24 takes the four-wave / pipelined kernels, a batch of 800
-the one-wave kernel) against the oracle's qoi_decode (codecs/qoi.d:448-550): a file the oracle decodes must come out byte for byte (a
-truncated stream decodes to the end of what is there and leaves the rest as the reference does), one it rejects must be rejected.
+"""Mutated QOI files through gamut_hip_qoi_decode_batch_device against the oracle's qoi_decode (codecs/qoi.d:448-550): a file the oracle decodes
+must come out byte for byte (a truncated stream decodes to the end of what is there and leaves the rest as the reference does), one it rejects must
+be rejected.  This reaches the four-wave / pipelined kernels ONLY: the host-memory entry launches at most 256 streams at a time (kGroup, qoi.hip), so
+a batch of 800 is four such launches, not one launch of the one-wave kernel (k_qoi_decode<1> starts from gamut_hip_qoi_decode_resident_device with at
+least 768 streams, which this tool does not call).  A clean run says nothing about that kernel.
 Usage: python tools/fuzz_qoi_gpu.py [batches=40] [seed=3]"""
 import ctypes as C
 import os
