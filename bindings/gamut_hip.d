@@ -186,7 +186,7 @@ extern(C)
                                      int max_bit_depth, int alpha_threshold, int* out_len);
     float gamut_hip_gif_last_encode_kernel_ms(int which);
 
-    // TGA: TGADecoder.getImageInfo / decodeImage on the GPU, decode only (codecs/tga.d:283-647, plugins/tga.d).  read_header gives two
+    // TGA: TGADecoder.getImageInfo / decodeImage on the GPU (codecs/tga.d:283-647, plugins/tga.d).  read_header gives two
     // verdicts: info.detected is detectTGA's, the return value the load's.  Deviation: width * height * components > int.max is refused.
     struct gamut_hip_tga_info { int width, height, bpp, image_type, rle, indexed, rgb16, channels_in_file, bottom_up, palette_start, palette_len,
                                 cmap_size, data_offset, detected; }
@@ -195,6 +195,16 @@ extern(C)
                                             ubyte* out_, gamut_hip_tga_info* info, int* status_host, void* stream);
     int   gamut_hip_tga_rle_window();
     float gamut_hip_tga_last_decode_kernel_ms();
+    // TGA encode: TGAEncoder as saveTGA drives it (codecs/tga.d:57-281, plugins/tga.d:128-150), byte for byte; comp is the source's
+    // channel count (1 l8, 2 la8, 3 rgb8, 4 rgba8).  Deviations: width or height 0 and a bound above int.max are refused.
+    long  gamut_hip_tga_encode_bound(int width, int height, int comp);
+    int   gamut_hip_tga_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(int)* width, const(int)* height,
+                                            const(int)* comp, const(int)* rle, int count, const(long)* out_offset, ubyte* out_,
+                                            long* out_len, int* status_host, void* stream);
+    void* gamut_hip_tga_write_to_mem(const(void)* data, int pitch, int w, int h, int comp, int rle, int* out_len);
+    int   gamut_hip_tga_encode_window();
+    float gamut_hip_tga_last_encode_kernel_ms();
+    float gamut_hip_tga_last_encode_stage_ms(int stage);
 
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }

@@ -135,6 +135,13 @@ SIGNATURES = {
     "gamut_hip_tga_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _i, C.POINTER(_i64), _vp, C.POINTER(TgaInfo), _pi, _vp]),
     "gamut_hip_tga_rle_window": (_i, []),
     "gamut_hip_tga_last_decode_kernel_ms": (_f, []),
+    "gamut_hip_tga_encode_bound": (_i64, [_i, _i, _i]),
+    "gamut_hip_tga_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), _pi, _pi, _pi, _pi, _i, C.POINTER(_i64), _vp,
+                                           C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_tga_write_to_mem": (_vp, [_vp, _i, _i, _i, _i, _i, _pi]),
+    "gamut_hip_tga_encode_window": (_i, []),
+    "gamut_hip_tga_last_encode_kernel_ms": (_f, []),
+    "gamut_hip_tga_last_encode_stage_ms": (_f, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

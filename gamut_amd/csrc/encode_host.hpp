@@ -1,4 +1,4 @@
-// encode_host.hpp -- what the host drop-ins that encode ONE image share (qoi_encode, jpeg_encode, png / bmp / gif _write_to_mem).
+// encode_host.hpp -- what the host drop-ins that encode ONE image share (qoi_encode, jpeg_encode, png / bmp / gif / tga _write_to_mem).
 #pragma once
 #include "common.hpp"
 

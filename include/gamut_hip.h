@@ -533,8 +533,8 @@ void*   gamut_hip_gif_write_to_mem(const void* data, int pitch, int64_t layer_of
  * offsets, 4: gather --, -1 when timing is off, nothing was encoded or `which` is out of range */
 float gamut_hip_gif_last_encode_kernel_ms(int which);
 
-/* ---- TGA (TGADecoder, codecs/tga.d:283-647; loadTGA / detectTGA, plugins/tga.d) -- decode only ------------------------------------
- * Every pixel what TGADecoder.decodeImage gives, bit for bit: image types 1 / 2 / 3 and their run-length forms 9 / 10 / 11, 8 / 15 /
+/* ---- TGA (TGADecoder / TGAEncoder, codecs/tga.d; loadTGA / detectTGA / saveTGA, plugins/tga.d) -----------------------------------
+ * Decode: every pixel what TGADecoder.decodeImage gives, bit for bit: image types 1 / 2 / 3 and their run-length forms 9 / 10 / 11, 8 / 15 /
  * 16 / 24 / 32 bits per pixel, colour maps of 8 / 15 / 16 / 24 / 32-bit entries under 8- or 16-bit indices, either row order.  Kept
  * from the reference: the colour map is reached by skipping palette_start BYTES (not entries); 15 / 16-bit pixels and colour-map
  * entries are (v * 255) / 31 per channel and are not R/B swapped; 16-bit grey is two raw bytes; a colour-map index >= palette_len
@@ -575,6 +575,32 @@ int   gamut_hip_tga_rle_window(void);
 /* measurements: with GAMUT_HIP_TGA_TIMING=1 the decode call brackets its kernels (not the upload) with events; this returns the GPU
  * milliseconds of the calling thread's last decode call, -1 when timing is off or nothing was decoded */
 float gamut_hip_tga_last_decode_kernel_ms(void);
+/* Encode: byte for byte TGAEncoder (codecs/tga.d:57-281) as saveTGA drives it (plugins/tga.d:128-150) -- 18 header bytes (type 10
+ * run-length or 2 raw, 24 or 32 bits, descriptor 0: rows bottom-up, no footer), B and R swapped, and with rle the reference's packets
+ * row by row.  comp is the SOURCE's channel count: 1 = l8 and 3 = rgb8 give 3 file channels (grey replicated), 2 = la8 and 4 = rgba8
+ * give 4.  Deliberate deviations: the reference refuses only a dimension above 65535 and the other pixel types; width or height 0 and
+ * a bound above 2^31 - 1 are refused here too.
+ * The most bytes a file can have, 18 + width * height * (file channels + 1) (reached at width 1), or 0 when the image is refused:
+ * width or height outside 1..65535, comp outside 1..4, a bound above 2^31 - 1. */
+int64_t gamut_hip_tga_encode_bound(int width, int height, int comp);
+/* batch: image i is read from DEVICE memory at src[i] (rows src_pitch[i] apart, negative allowed, any alignment) and written to
+ * out + out_offset[i] (device, any alignment), which must have gamut_hip_tga_encode_bound(...) bytes; nothing outside
+ * [out_offset[i], out_offset[i] + out_len[i]) is written.  rle: 0 / 1 per image, NULL for 1 everywhere (saveTGA's choice).
+ * out_len[i] / status_host[i] (host arrays; status_host may be NULL) are filled when the call returns: a refused image (or a NULL
+ * src[i], a negative out_offset[i]) gets GAMUT_HIP_ERR_INVALID_ARG and out_len 0, the others are still encoded, and the call returns
+ * the status of the lowest-numbered refused image.  Three launches, whatever the batch holds. */
+int     gamut_hip_tga_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const int32_t* width,
+                                          const int32_t* height, const int32_t* comp, const int32_t* rle, int count,
+                                          const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host, void* stream);
+/* host pixels (rows `pitch` bytes apart, negative allowed) through pinned staging -> malloc'd file of *out_len bytes, or NULL on
+ * refusal (see last_error) */
+void*   gamut_hip_tga_write_to_mem(const void* data, int pitch, int w, int h, int comp, int rle, int* out_len);
+/* the encoder assembles a row's packets this many pixels at a time (a row wider than this is written in several pieces) */
+int     gamut_hip_tga_encode_window(void);
+/* measurements, under GAMUT_HIP_TGA_TIMING=1 as the decode getter: the GPU milliseconds of the calling thread's last encode call --
+ * all three launches, or one of them (0 row lengths, 1 offsets, 2 write); -1 when timing is off or nothing was encoded */
+float   gamut_hip_tga_last_encode_kernel_ms(void);
+float   gamut_hip_tga_last_encode_stage_ms(int stage);
 
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect

@@ -152,6 +152,12 @@ int      gamut_image_save_png_to_file(gamut_image* img, const char* path, int fl
  * ignored as saveBMP ignores them.  The image's state and error are left as they were.  Freed with gamut_free_encoded_image. */
 uint8_t* gamut_image_save_bmp_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
 int      gamut_image_save_bmp_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
+/* saveTGA (plugins/tga.d:128-150; gamut_hip_tga_encode*): l8 / la8 / rgb8 / rgba8, every other type refused as TGAEncoder.initialize
+ * refuses it; layer 0 of a layered image (saveTGA walks scanptr(y)); always run-length encoded, flags are ignored; 1 <= width, height
+ * <= 65535.  GAMUT_FORMAT_TGA (5) is not dispatched from the two generic entries above (they return NULL / 0 for it).  The image's
+ * state and error are left as they were.  Freed with gamut_free_encoded_image. */
+uint8_t* gamut_image_save_tga_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
+int      gamut_image_save_tga_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
 
 #ifdef __cplusplus
 }
