@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <chrono>
 #include <memory>
 #include <new>
 #include <algorithm>
@@ -135,6 +136,39 @@ struct PinnedScratch {                  // page-locked host memory: uploads from
         last_user = stream;
         return p;
     }
+};
+
+// stage timings on stderr (GAMUT_HIP_TRACE, tools/e2e_bench.py)
+using TracePoint = std::chrono::steady_clock::time_point;
+inline bool trace_enabled() { return getenv("GAMUT_HIP_TRACE") != nullptr; }
+inline TracePoint trace_now() { return std::chrono::steady_clock::now(); }
+inline double ms_since(TracePoint t0) { return std::chrono::duration<double, std::milli>(trace_now() - t0).count(); }
+
+// The per-thread staging of a call (pinned images, device scratch) is reused by the thread's next call: no way out of a call may leave
+// a stream behind that still reads or writes it.  Armed with the call's stream once the first asynchronous operation on the staging is
+// queued; streams the call opens besides it are added as they come into use.  wait() is the success path's synchronise -- the added
+// streams in the order they were added, then the call's own -- and tells the first failure; every other way out waits in the
+// destructor, where the results are ignored and the thread's error message is left as it is.
+struct StreamDrain {
+    static constexpr int kMaxAdded = 8;
+    hipStream_t added[kMaxAdded] = {}; int n_added = 0;
+    hipStream_t last = nullptr; bool armed = false;
+    void arm(hipStream_t call_stream) { last = call_stream; armed = true; }
+    void add(hipStream_t s) { if (n_added < kMaxAdded) added[n_added++] = s; }
+    hipError_t wait()
+    {
+        armed = false;
+        hipError_t first = hipSuccess;
+        for (int k = 0; k <= n_added; ++k) {
+            const hipError_t e = hipStreamSynchronize(k < n_added ? added[k] : last);
+            if (first == hipSuccess) first = e;
+        }
+        return first;
+    }
+    StreamDrain() = default;
+    StreamDrain(const StreamDrain&) = delete;
+    StreamDrain& operator=(const StreamDrain&) = delete;
+    ~StreamDrain() { if (armed) (void)wait(); }
 };
 
 // Measurements: N marks on a call's stream, and the GPU milliseconds between consecutive marks for the codec's *_last_*_kernel_ms

@@ -1,6 +1,6 @@
 // jpeg_batch.hpp -- batch orchestration of the baseline device entropy decode.  Included by jpeg_host.hip inside its namespace, behind
 // jpeg_parse.hpp (the marker parser) and jpeg_entropy_kernels.hpp (the device structs and kernels), in front of jpeg_prog.hpp (which
-// shares the helpers at the top of this file).
+// shares the helpers at the top of this file; the stream guard and the trace clock are common.hpp's).
 //
 // Host side: header walk per file (on host threads), table de-duplication, restart-interval index, uploads per group of files and the
 // groups' kernels; entropy_decode_device at the end of the file is the list of the stages.
@@ -18,39 +18,6 @@ struct ParserPool {
     explicit ParserPool(int workers) { for (int w = 0; w < workers; ++w) parsers.emplace_back(new Parser()); }
     Parser& operator[](int w) { return *parsers[(size_t)w]; }
 };
-// stage timings on stderr (GAMUT_HIP_TRACE, tools/e2e_bench.py)
-using TracePoint = std::chrono::steady_clock::time_point;
-inline bool trace_enabled() { return getenv("GAMUT_HIP_TRACE") != nullptr; }
-inline TracePoint trace_now() { return std::chrono::steady_clock::now(); }
-inline double ms_since(TracePoint t0) { return std::chrono::duration<double, std::milli>(trace_now() - t0).count(); }
-
-// The per-thread staging of a call (pinned images, device scratch) is reused by the thread's next call: no way out of a call may leave
-// a stream behind that still reads or writes it.  Armed with the call's stream once the first asynchronous operation on the staging is
-// queued; streams the call opens besides it are added as they come into use.  wait() is the success path's synchronise -- the added
-// streams in the order they were added, then the call's own -- and tells the first failure; every other way out waits in the
-// destructor, where the results are ignored and the thread's error message is left as it is.
-struct StreamDrain {
-    static constexpr int kMaxAdded = 8;
-    hipStream_t added[kMaxAdded] = {}; int n_added = 0;
-    hipStream_t last = nullptr; bool armed = false;
-    void arm(hipStream_t call_stream) { last = call_stream; armed = true; }
-    void add(hipStream_t s) { if (n_added < kMaxAdded) added[n_added++] = s; }
-    hipError_t wait()
-    {
-        armed = false;
-        hipError_t first = hipSuccess;
-        for (int k = 0; k <= n_added; ++k) {
-            const hipError_t e = hipStreamSynchronize(k < n_added ? added[k] : last);
-            if (first == hipSuccess) first = e;
-        }
-        return first;
-    }
-    StreamDrain() = default;
-    StreamDrain(const StreamDrain&) = delete;
-    StreamDrain& operator=(const StreamDrain&) = delete;
-    ~StreamDrain() { if (armed) (void)wait(); }
-};
-
 template <class T> int intern(std::vector<T>& pool, const T& t)      // index of a bit-identical table, appended if new
 {
     for (size_t i = 0; i < pool.size(); ++i) if (!memcmp(&pool[i], &t, sizeof(T))) return (int)i;

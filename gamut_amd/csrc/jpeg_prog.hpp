@@ -1,6 +1,6 @@
 // jpeg_prog.hpp -- progressive (SOF2) entropy decode ON THE GPU.  Included by jpeg_host.hip inside its namespace, behind
 // jpeg_parse.hpp (the marker parser, the host feeder that is its oracle), jpeg_entropy_kernels.hpp (DevHuff, the bit reader) and
-// jpeg_batch.hpp (the marker walk of the unstuffers, host_redo, the stream guard and the small batch helpers).
+// jpeg_batch.hpp (the marker walk of the unstuffers, host_redo and the small batch helpers); the stream guard is common.hpp's.
 //
 // A progressive file is a sequence of scans (jpegload.d:3296-3664): DC first / DC refinement (all components, coefficient 0)
 // and, per component, AC first / AC refinement scans over a band [Ss, Se] of the zig-zag order, each refining the bits the

@@ -1,204 +1,16 @@
-// png_host.hip -- host side of the PNG path and its C-ABI entry points.
+// png_host.hip -- device side of the PNG path as the host drives it, and its C-ABI entry points.
 //
-// Host feeder = what stays on the CPU in the reference too:
-// the chunk walk of stbi__parse_png_file (stbdec.d:1777-2023: IHDR/PLTE/tRNS/pHYs/CgBI/IDAT,
-// missing-IEND tolerance :2008-2012) and the inflate of finalize_decode (:1808-1819; the
-// reference calls the third-party `miniz`, here the system zlib in raw mode with the adler32
-// unchecked like the reference's trusted_input=true).  Everything after the inflate runs on
+// The file itself -- the chunk walk of stbi__parse_png_file, the inflate of finalize_decode, which stay on the CPU in the reference
+// too -- is png_file.hip's.  Everything after the inflate runs on
 // the GPU: de-filter / expand (png.hip), Adam7 scatter, tRNS, palette, channel and depth
 // conversion, in the order of finalize_decode (:1821-1857) and stbi__do_png (:2025-2055).
-#include "common.hpp"
-#include <algorithm>
-#include <atomic>
-#include <chrono>
+#include "png_file.hpp"
 #include <map>
 #include <mutex>
-#include <thread>
 #include <tuple>
-#include <vector>
-#include <zlib.h>
 
 namespace gamut {
 namespace {
-
-struct Reader {                       // stb's memory reader: reads past the end yield 0 (stbi__get8)
-    const uint8_t* p; const uint8_t* end;
-    int      get8()    { return p < end ? *p++ : 0; }
-    uint32_t get16be() { uint32_t z = (uint32_t)get8(); return (z << 8) + (uint32_t)get8(); }
-    uint32_t get32be() { uint32_t z = get16be(); return (z << 16) + get16be(); }
-    bool     eof() const { return p >= end; }
-    void     skip(uint32_t n) { if ((size_t)(end - p) < n) p = end; else p += n; }
-};
-
-struct PngHeader {
-    uint32_t x = 0, y = 0; int depth = 0, color = 0, interlace = 0, img_n = 0, pal_img_n = 0;
-    bool has_trans = false, is_iphone = false;
-    uint8_t palette[1024] = {}; uint32_t pal_len = 0;     // zero-initialised like the D array (stbdec.d:1779): indices >= pal_len expand to (0,0,0,0)
-    uint16_t tc[3] = { 0, 0, 0 };      // tRNS key: 8-bit values already scaled (stbdec.d:1945), 16-bit as-is (:1941)
-    float ppmX = -1, ppmY = -1, aspect = -1;
-    uint8_t* idata = nullptr; uint32_t ioff = 0;
-    // the batch path that inflates on the GPU gathers the IDAT payloads itself, slice by slice: parse() then only notes where they are
-    std::vector<std::pair<const uint8_t*, uint32_t>>* idat_segments = nullptr;
-    bool seen_idat = false;
-    ~PngHeader() { free(idata); }
-};
-
-const uint8_t kDepthScale[9] = { 0, 0xff, 0x55, 0, 0x11, 0, 0, 0, 0x01 };
-constexpr uint32_t fourcc(char a, char b, char c, char d) { return ((uint32_t)(uint8_t)a << 24) | ((uint32_t)(uint8_t)b << 16) | ((uint32_t)(uint8_t)c << 8) | (uint8_t)d; }
-
-// header_only: stop as stbi__png_info_raw does (SCAN_header), enough for stbi__png_is16
-int parse(const uint8_t* data, size_t len, PngHeader& h, bool header_only)
-{
-    static const uint8_t sig[8] = { 137, 80, 78, 71, 13, 10, 26, 10 };
-    Reader s{ data, data + len };
-    for (int i = 0; i < 8; ++i) if (s.get8() != sig[i]) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad signature");
-    bool first = true; uint32_t cap = 0;
-    for (;;) {
-        const uint32_t clen = s.get32be(), type = s.get32be();
-        switch (type) {
-        case fourcc('C','g','B','I'): h.is_iphone = true; s.skip(clen); break;
-        case fourcc('p','H','Y','s'):
-            h.ppmX = (float)s.get32be(); h.ppmY = (float)s.get32be(); h.aspect = h.ppmX / h.ppmY;
-            if (s.get8() != 1) { h.ppmX = -1; h.ppmY = -1; }
-            break;
-        case fourcc('I','H','D','R'): {
-            if (!first || clen != 13) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad IHDR");
-            first = false;
-            h.x = s.get32be(); h.y = s.get32be();
-            if (h.y > (1u << 24) || h.x > (1u << 24)) return set_error(GAMUT_HIP_ERR_DECODE, "png: too large");
-            h.depth = s.get8();
-            if (h.depth != 1 && h.depth != 2 && h.depth != 4 && h.depth != 8 && h.depth != 16) return set_error(GAMUT_HIP_ERR_DECODE, "png: 1/2/4/8/16-bit only");
-            h.color = s.get8();
-            if (h.color > 6 || (h.color == 3 && h.depth == 16)) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad ctype");
-            if (h.color == 3) h.pal_img_n = 3; else if (h.color & 1) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad ctype");
-            if (s.get8()) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad comp method");
-            if (s.get8()) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad filter method");
-            h.interlace = s.get8(); if (h.interlace > 1) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad interlace method");
-            if (!h.x || !h.y) return set_error(GAMUT_HIP_ERR_DECODE, "png: 0-pixel image");
-            if (!h.pal_img_n) {
-                h.img_n = (h.color & 2 ? 3 : 1) + (h.color & 4 ? 1 : 0);
-                if ((1u << 30) / h.x / (uint32_t)h.img_n < h.y) return set_error(GAMUT_HIP_ERR_DECODE, "png: too large");
-                if (header_only) return GAMUT_HIP_OK;
-            } else {
-                h.img_n = 1;
-                if ((1u << 30) / h.x / 4 < h.y) return set_error(GAMUT_HIP_ERR_DECODE, "png: too large");
-            }
-        } break;
-        case fourcc('P','L','T','E'):
-            if (first || clen > 256 * 3) return set_error(GAMUT_HIP_ERR_DECODE, "png: invalid PLTE");
-            h.pal_len = clen / 3;
-            if (h.pal_len * 3 != clen) return set_error(GAMUT_HIP_ERR_DECODE, "png: invalid PLTE");
-            for (uint32_t i = 0; i < h.pal_len; ++i) {
-                h.palette[i*4] = (uint8_t)s.get8(); h.palette[i*4+1] = (uint8_t)s.get8(); h.palette[i*4+2] = (uint8_t)s.get8(); h.palette[i*4+3] = 255;
-            }
-            break;
-        case fourcc('t','R','N','S'):
-            if (first) return set_error(GAMUT_HIP_ERR_DECODE, "png: first not IHDR");
-            if (h.idata || h.seen_idat) return set_error(GAMUT_HIP_ERR_DECODE, "png: tRNS after IDAT");
-            if (h.pal_img_n) {
-                if (header_only) { h.img_n = 4; return GAMUT_HIP_OK; }
-                if (h.pal_len == 0 || clen > h.pal_len) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad tRNS");
-                h.pal_img_n = 4;
-                for (uint32_t i = 0; i < clen; ++i) h.palette[i*4+3] = (uint8_t)s.get8();
-            } else {
-                if (!(h.img_n & 1) || clen != (uint32_t)h.img_n * 2) return set_error(GAMUT_HIP_ERR_DECODE, "png: bad tRNS");
-                h.has_trans = true;
-                for (int k = 0; k < h.img_n; ++k) {
-                    const uint32_t v = s.get16be();
-                    h.tc[k] = h.depth == 16 ? (uint16_t)v : (uint16_t)(uint8_t)((uint8_t)(v & 255) * kDepthScale[h.depth]);
-                }
-            }
-            break;
-        case fourcc('I','D','A','T'): {
-            if (first) return set_error(GAMUT_HIP_ERR_DECODE, "png: first not IHDR");
-            if (h.pal_img_n && !h.pal_len) return set_error(GAMUT_HIP_ERR_DECODE, "png: no PLTE");
-            if (header_only) { h.img_n = h.pal_img_n ? h.pal_img_n : h.img_n; return GAMUT_HIP_OK; }
-            if ((int32_t)(h.ioff + clen) < (int32_t)h.ioff) return set_error(GAMUT_HIP_ERR_DECODE, "png: IDAT overflow");
-            h.seen_idat = true;
-            if (h.idat_segments) {
-                if ((size_t)(s.end - s.p) < clen) return set_error(GAMUT_HIP_ERR_DECODE, "png: out of data");
-                if (clen) h.idat_segments->emplace_back(s.p, clen);
-                s.p += clen; h.ioff += clen;
-                break;
-            }
-            if (h.ioff + clen > cap) {
-                uint32_t ncap = cap ? cap : (clen > 4096 ? clen : 4096);
-                while (h.ioff + clen > ncap) ncap *= 2;
-                uint8_t* n = (uint8_t*)realloc(h.idata, ncap);
-                if (!n) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: out of memory");
-                h.idata = n; cap = ncap;
-            }
-            if ((size_t)(s.end - s.p) < clen) return set_error(GAMUT_HIP_ERR_DECODE, "png: out of data");
-            memcpy(h.idata + h.ioff, s.p, clen); s.p += clen; h.ioff += clen;
-        } break;
-        case fourcc('I','E','N','D'):
-            if (first) return set_error(GAMUT_HIP_ERR_DECODE, "png: first not IHDR");
-            return GAMUT_HIP_OK;
-        default:
-            if (first) return set_error(GAMUT_HIP_ERR_DECODE, "png: first not IHDR");
-            if (type == 0 && s.eof()) return GAMUT_HIP_OK;                 // Gamut issue #92: no IEND
-            if ((type & (1u << 29)) == 0) return set_error(GAMUT_HIP_ERR_DECODE, "png: unknown critical chunk");
-            s.skip(clen);
-            break;
-        }
-        s.get32be();      // CRC, not checked
-    }
-}
-
-// Where zlib writes the inflated stream.  Page-locked (the per-thread staging of the single-image calls: the upload is
-// then a plain DMA -- an upload from freshly written pageable memory was seen to take 12-22 ms for 4 MB on some boxes,
-// 0.2 ms on others; intentionally not freed at thread exit, the HIP runtime may already be gone) or plain malloc memory
-// (the short-lived worker threads of the batch call).
-struct HostBuf {
-    uint8_t* p = nullptr; size_t cap = 0; bool pinned = false;
-    bool reserve(size_t n, size_t keep)
-    {
-        if (n <= cap) return true;
-        const size_t ncap = n + n / 8 + 4096;
-        if (pinned) {
-            void* np = nullptr;
-            if (hipHostMalloc(&np, ncap, hipHostMallocDefault) != hipSuccess) return false;
-            if (keep) memcpy(np, p, keep);
-            if (p) (void)hipHostFree(p);
-            p = (uint8_t*)np;
-        } else {
-            uint8_t* np = (uint8_t*)realloc(p, ncap);
-            if (!np) return false;
-            p = np;
-        }
-        cap = ncap;
-        return true;
-    }
-    void release() { if (p) { if (pinned) (void)hipHostFree(p); else free(p); } p = nullptr; cap = 0; }
-};
-
-// stbi_zlib_decode_malloc_guesssize_headerflag (stbdec.d:1267-1321); the result lives in `out` (not to be freed)
-uint8_t* inflate_idat(const uint8_t* buf, uint32_t len, size_t guess, uint32_t* outlen, bool parse_header, HostBuf& out)
-{
-    if (parse_header) {
-        if (len < 2 || ((buf[0] * 256 + buf[1]) % 31) != 0 || (buf[1] & 32) || (buf[0] & 15) != 8) { set_error(GAMUT_HIP_ERR_DECODE, "png: bad zlib header"); return nullptr; }
-        buf += 2; len -= 2;
-    }
-    size_t cap = guess ? guess : 1;
-    z_stream z; memset(&z, 0, sizeof(z));
-    if (!out.reserve(cap, 0) || inflateInit2(&z, -15) != Z_OK) { set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: inflate init failed"); return nullptr; }
-    z.next_in = const_cast<Bytef*>(buf); z.avail_in = len; z.next_out = out.p; z.avail_out = (uInt)cap;
-    for (;;) {
-        const int r = inflate(&z, Z_NO_FLUSH);
-        if (r == Z_STREAM_END) break;
-        if ((r == Z_OK || r == Z_BUF_ERROR) && z.avail_out == 0 && cap <= 536870912u) {
-            size_t ncap = cap * 2; if (ncap < 32 * 1024) ncap = 32 * 1024;
-            if (!out.reserve(ncap, cap)) { inflateEnd(&z); set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: out of memory"); return nullptr; }
-            z.next_out = out.p + cap; z.avail_out = (uInt)(ncap - cap); cap = ncap;
-            continue;
-        }
-        if (r == Z_OK && z.avail_in != 0) continue;
-        inflateEnd(&z); set_error(GAMUT_HIP_ERR_DECODE, "png: corrupt zlib stream"); return nullptr;
-    }
-    *outlen = (uint32_t)z.total_out;
-    inflateEnd(&z);
-    return out.p;
-}
 
 struct Dev {
     void* p = nullptr;
@@ -207,29 +19,16 @@ struct Dev {
     void swap(Dev& o) { void* t = p; p = o.p; o.p = t; }
 };
 
-// parse + inflate of one file (host only)
-struct PngJob { PngHeader h; HostBuf raw; uint32_t raw_len = 0; int rc = GAMUT_HIP_OK; char msg[160] = { 0 }; };
-
-int png_prepare(const uint8_t* data, size_t len, PngJob& j)
-{
-    if (parse(data, len, j.h, false)) return j.rc = GAMUT_HIP_ERR_DECODE;
-    if (!j.h.idata) return j.rc = set_error(GAMUT_HIP_ERR_DECODE, "png: no IDAT");
-    const uint32_t bpl = (j.h.x * (uint32_t)j.h.depth + 7) / 8;
-    if (!inflate_idat(j.h.idata, j.h.ioff, (size_t)bpl * j.h.y * j.h.img_n + j.h.y, &j.raw_len, !j.h.is_iphone, j.raw)) return j.rc = GAMUT_HIP_ERR_DECODE;
-    return j.rc = GAMUT_HIP_OK;
-}
-
 // The whole of stbi__do_png after the inflate, on the GPU: de-filter (+ Adam7), tRNS, palette, channel-count conversion
 // (stbdec.d:1646-1679, 1821-1855, 2038-2045), then the 16 <-> 8 step of stbi__load_and_postprocess_* (:669-707) when
 // want_bits (8 / 16; 0 = as decoded) asks for it.  The result is left at d_dst (device) or returned as malloc'd host memory.
 uint8_t* png_run(const PngHeader& h, const uint8_t* raw, uint32_t raw_len, int req_comp, int want_bits, uint8_t* d_dst,
                  int* px, int* py, int* pn, int* bits_out, hipStream_t st, const uint8_t* d_raw = nullptr)
 {
-    const bool trace = getenv("GAMUT_HIP_TRACE") != nullptr;               // stage timings on stderr
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    int img_n = h.img_n, out_n;
-    if ((req_comp == img_n + 1 && req_comp != 3 && !h.pal_img_n) || h.has_trans) out_n = img_n + 1; else out_n = img_n;   // :1821-1824
+    const bool trace = trace_enabled();                                    // stage timings on stderr
+    const auto now = trace_now;
+    auto ms = [](TracePoint a, TracePoint b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    int img_n = h.img_n, out_n = png_out_channels(h, req_comp);
     int bytes = h.depth == 16 ? 2 : 1;
     const int64_t npx = (int64_t)h.x * h.y;
 
@@ -320,11 +119,11 @@ uint8_t* png_load(const uint8_t* data, size_t len, int* px, int* py, int* pn, in
     static thread_local PerDevice<Staging> staging_pd;
     HostBuf& staging = staging_pd.cur().b;
     PngJob j; j.raw = staging;                                               // borrow the per-thread pinned buffer
-    const auto t0 = std::chrono::steady_clock::now();
+    const TracePoint t0 = trace_now();
     const int rc = png_prepare(data, len, j);
     staging = j.raw; j.raw = HostBuf{};                                      // hand it back (it may have grown)
     if (rc != GAMUT_HIP_OK) return nullptr;
-    if (getenv("GAMUT_HIP_TRACE")) fprintf(stderr, "[gamut_hip] png parse + inflate %.2f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (trace_enabled()) fprintf(stderr, "[gamut_hip] png parse + inflate %.2f ms\n", ms_since(t0));
     if (ppmX) *ppmX = j.h.ppmX;
     if (ppmY) *ppmY = j.h.ppmY;
     if (aspect) *aspect = j.h.aspect;
@@ -341,16 +140,381 @@ struct PinnedPool {
 };
 PinnedPool& pinned_pool() { static PinnedPool* p = new PinnedPool(); return *p; }
 
+// Host threads that all run one callable, joined at the latest when the object goes out of scope: no way out of a stage leaves a thread
+// behind that reads the stage's data.  A thread that cannot be started is done without -- the work is handed out dynamically, so
+// the threads that did start (and the caller) take it.
+struct HostThreads {
+    std::vector<std::thread> pool;
+    template <class Fn> int start(int n, Fn fn) { try { for (int t = 0; t < n; ++t) pool.emplace_back(fn); } catch (...) {} return (int)pool.size(); }
+    void join() { for (std::thread& th : pool) th.join(); pool.clear(); }
+    ~HostThreads() { join(); }
+};
+template <class Fn> void run_on_threads(int threads, Fn fn) { HostThreads pool; pool.start(threads - 1, fn); fn(); }      // the caller is one of them
+
+// The events the compute stream waits on, one or two per slice round; destroyed on every way out.
+struct SliceEvents {
+    std::vector<hipEvent_t> ev;
+    // a new event, recorded on `from`, that `to` waits for (false: HIP refused; what was made of the event is still owned)
+    bool chain(hipStream_t from, hipStream_t to)
+    {
+        ev.push_back(nullptr);
+        return hipEventCreateWithFlags(&ev.back(), hipEventDisableTiming) == hipSuccess && hipEventRecord(ev.back(), from) == hipSuccess &&
+               hipStreamWaitEvent(to, ev.back(), 0) == hipSuccess;
+    }
+    void destroy() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); ev.clear(); }
+    ~SliceEvents() { destroy(); }
+};
+
+// Batch: chunk walk + inflate on host threads, one file per thread at a time, into pinned memory; the inflated stream goes
+// to a device arena at once (copy stream).  Files that need nothing but de-filter + expand (batched(), png_file.hpp) are then
+// de-filtered TOGETHER, one launch per geometry with one workgroup per image (a 4K image alone occupies one CU for 4.5 ms; 64 of
+// them side by side take about as long).  The others run the whole of stbi__do_png one after the other.
+//
 // Batches with more files than host threads inflate on the GPU (one workgroup per stream): a stream takes the kernel 0.8-3 times as long
 // as it takes zlib on one host core, but up to 256 of them run side by side -- the host threads need a second round of files from
 // threads + 1 files on (16 threads, 4K files: 16 files 64 / 40 ms on the host against 75 / 52 ms on the device, 24 files 112 / 67 against 75 / 51).
-
-struct BatchFile {                    // what a worker leaves behind for one file
-    int rc = GAMUT_HIP_OK; char msg[160] = { 0 };
-    bool uploaded = false, batched = false;   // inflated stream in the device arena; de-filter goes into a batched launch
-    PngHeader h;                      // (idata released)
-    uint32_t raw_len = 0, need = 0; int out_n = 0, bits = 8, channels_in_file = 0;
+//
+// One call of gamut_hip_png_decode_batch_device: what its stages share.  The stages, in the order of the entry point:
+// plan_arena -> run_host_stage (inflate_worker | walk_worker) -> inflate_on_device (plan_device_inflate, launch_slices with
+// upload_worker beside launch_round, collect_verdicts) -> defilter_batched -> decode_remaining -> report.
+struct PngBatch {
+    // the arguments
+    const uint8_t* const* data; const size_t* len; int count, req_comp, bits;
+    const int64_t* out_offset; uint8_t* out; gamut_hip_png_info* info; int* status_host; int threads; hipStream_t st;
+    int dev = 0;
+    // The calling thread's copy streams (per device).  Worker threads take them from here and never from a thread_local: a worker would
+    // read ITS OWN (null) instance and upload on the legacy null stream.
+    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr;
+    // per file: the verdict so far, the slot in the device arena for the inflated stream (-1: none)
+    std::vector<BatchFile> files; std::vector<int64_t> slot, slot_bytes; int64_t arena_bytes = 0; uint8_t* d_arena = nullptr;
+    // the host stage
+    bool device_inflate = false; std::atomic<int> next{ 0 }; std::atomic<int64_t> us_inflate{ 0 }, us_upload{ 0 };
+    // the device inflate: where the IDAT payloads lie in the files, the zlib stream of file i = its payloads without idat_skip[i] bytes
+    std::vector<IdatSegments> segments; std::vector<uint32_t> idat_len, idat_skip;
+    SlicePlan plan; uint8_t* h_blob = nullptr; uint8_t* d_blob = nullptr; uint32_t* d_verdict = nullptr;
+    std::vector<std::atomic<int>> round_done; std::atomic<size_t> next_unit{ 0 }; std::atomic<bool> upload_failed{ false };
+    std::vector<std::vector<uint32_t>> avail;              // (one table per launch, alive until the stream has been waited for)
+    std::vector<uint32_t> verdict;                         // [0, n): inflated length, [n, 2n): status, per stream of the plan
+    // the batched de-filter: files by geometry, their order in the launches, the offset tables and the status words
+    std::map<std::tuple<uint32_t, uint32_t, int, int, int, int>, std::vector<int>> groups;
+    std::vector<int> order; std::vector<int64_t> offs; std::vector<uint32_t> status; int n_batched = 0;
+    // trace (GAMUT_HIP_TRACE)
+    const bool trace = trace_enabled(); TracePoint t_begin; double ms_workers = 0, ms_device_inflate = 0;
+    // Last, so that they go first: every way out of the call waits for the streams it used BEFORE the host memory above, which
+    // downloads write into, is released; then the events go.
+    SliceEvents events; StreamDrain drain;
 };
+
+// IHDR of every file: a slot in the device arena for its inflated stream
+int plan_arena(PngBatch& b)
+{
+    static thread_local PerDevice<hipStream_t> copy_stream_pd;
+    hipStream_t& copy_stream = copy_stream_pd.cur();
+    if (!copy_stream) GAMUT_HIP_CHECK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    b.copy_stream = copy_stream;
+    const size_t count = (size_t)b.count;
+    b.files.resize(count); b.slot.assign(count, -1); b.slot_bytes.assign(count, 0);
+    for (size_t i = 0; i < count; ++i) {
+        PngHeader h;
+        if (parse(b.data[i], b.len[i], h, true)) continue;                   // the worker reports the error
+        const uint64_t room = h.slot_bytes();
+        if (room > kMaxSlotBytes) continue;
+        b.slot[i] = b.arena_bytes; b.slot_bytes[i] = (int64_t)room; b.arena_bytes += (int64_t)up256(room);
+    }
+    clear_error();
+    static thread_local PerDevice<DeviceScratch> arena_pd;
+    b.d_arena = b.arena_bytes ? (uint8_t*)arena_pd.cur().get((size_t)b.arena_bytes, b.st) : nullptr;
+    if (b.arena_bytes && !b.d_arena) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: device arena of %lld bytes failed", (long long)b.arena_bytes);
+    b.drain.arm(b.st); b.drain.add(b.copy_stream);          // from here on every way out of the call waits for the streams it used
+    return GAMUT_HIP_OK;
+}
+
+// Host inflate: chunk walk + inflate into the worker's pinned buffer, and the stream goes to the arena at once
+void inflate_worker(PngBatch& b)
+{
+    (void)hipSetDevice(b.dev);
+    HostBuf buf = pinned_pool().take();
+    hipEvent_t copied = nullptr;
+    (void)hipEventCreateWithFlags(&copied, hipEventDisableTiming);
+    for (int i; (i = b.next.fetch_add(1, std::memory_order_relaxed)) < b.count; ) {
+        BatchFile& f = b.files[(size_t)i];
+        PngJob j; j.raw = buf;                                           // borrow the worker's pinned buffer
+        const TracePoint t_in = trace_now();
+        const int rc = png_prepare(b.data[i], b.len[i], j);
+        buf = j.raw; j.raw = HostBuf{};
+        b.us_inflate += (int64_t)(ms_since(t_in) * 1000);
+        if (rc != GAMUT_HIP_OK) { f.fail(i, rc, last_error_buf()); continue; }
+        free(j.h.idata); j.h.idata = nullptr;
+        f.accept(j.h, b.req_comp);
+        if (b.slot[(size_t)i] < 0) { f.fail(i, GAMUT_HIP_ERR_DECODE, "png: image too large"); continue; }
+        if (!copied) { f.fail(i, GAMUT_HIP_ERR_HIP, "png: event creation failed"); continue; }
+        f.raw_len = (uint32_t)std::min<int64_t>((int64_t)j.raw_len, b.slot_bytes[(size_t)i]);
+        const TracePoint t_upl = trace_now();
+        if (hipMemcpyAsync(b.d_arena + b.slot[(size_t)i], buf.p, f.raw_len, hipMemcpyHostToDevice, b.copy_stream) != hipSuccess ||
+            hipEventRecord(copied, b.copy_stream) != hipSuccess || hipEventSynchronize(copied) != hipSuccess) {
+            f.fail(i, GAMUT_HIP_ERR_HIP, "png: upload failed"); continue;
+        }
+        b.us_upload += (int64_t)(ms_since(t_upl) * 1000);
+        f.uploaded = true;
+        f.batched = batched(f, b.req_comp, b.bits);
+    }
+    if (copied) (void)hipEventDestroy(copied);
+    pinned_pool().give(buf);
+}
+
+// Device inflate, step one: the chunk walk of every file (no byte of IDAT data is touched: parse() notes where the payloads are)
+void walk_worker(PngBatch& b)
+{
+    (void)hipSetDevice(b.dev);
+    for (int i; (i = b.next.fetch_add(1, std::memory_order_relaxed)) < b.count; ) {
+        BatchFile& f = b.files[(size_t)i];
+        const IdatSegments& segments = b.segments[(size_t)i];
+        PngHeader h;
+        h.idat_segments = &b.segments[(size_t)i];
+        const TracePoint t_in = trace_now();
+        int rc = parse(b.data[i], b.len[i], h, false);
+        if (rc == GAMUT_HIP_OK && !h.seen_idat) rc = set_error(GAMUT_HIP_ERR_DECODE, "png: no IDAT");
+        uint32_t skip = 0;
+        if (rc == GAMUT_HIP_OK && !h.is_iphone) {                       // the zlib header, as inflate_idat checks it
+            uint8_t hd[2] = { 0, 0 };
+            copy_idat_range(segments, 0, 0, std::min<uint32_t>(h.ioff, 2), hd);
+            if (h.ioff < 2 || !zlib_header_ok(hd[0], hd[1])) rc = set_error(GAMUT_HIP_ERR_DECODE, "png: bad zlib header");
+            skip = 2;
+        }
+        if (rc == GAMUT_HIP_OK && b.slot[(size_t)i] < 0) rc = set_error(GAMUT_HIP_ERR_DECODE, "png: image too large");
+        if (rc != GAMUT_HIP_OK) { f.fail(i, rc, last_error_buf()); continue; }
+        b.idat_len[(size_t)i] = h.ioff - skip;
+        b.idat_skip[(size_t)i] = skip;
+        h.idat_segments = nullptr;
+        f.accept(h, b.req_comp);
+        b.us_inflate += (int64_t)(ms_since(t_in) * 1000);
+    }
+}
+
+// The host stage: the files over the host threads.  Inflate on the GPU (inflate.hip) when the batch is large enough to beat the host
+// threads: the workers then only walk the chunks.  GAMUT_HIP_PNG_INFLATE=host / device overrides the choice.
+int run_host_stage(PngBatch& b)
+{
+    b.t_begin = trace_now();
+    b.device_inflate = b.count > b.threads;                  // (threads <= count here)
+    if (const char* v = getenv("GAMUT_HIP_PNG_INFLATE")) b.device_inflate = strcmp(v, "device") == 0 ? true : strcmp(v, "host") == 0 ? false : b.device_inflate;
+    b.idat_len.assign((size_t)b.count, 0); b.idat_skip.assign((size_t)b.count, 0);
+    if (b.device_inflate) {
+        b.segments.resize((size_t)b.count);
+        run_on_threads(b.threads, [&b] { walk_worker(b); });
+    } else {
+        run_on_threads(b.threads, [&b] { inflate_worker(b); });
+    }
+    clear_error();
+    GAMUT_HIP_CHECK(hipStreamSynchronize(b.copy_stream));                         // (every worker waited for its own copies already)
+    return GAMUT_HIP_OK;
+}
+
+// Device inflate, the plan: which streams, the slices and the layout of the staging image (plan_slices), the staging itself
+int plan_device_inflate(PngBatch& b)
+{
+    std::vector<int> streams;
+    for (int i = 0; i < b.count; ++i) if (b.files[(size_t)i].rc == GAMUT_HIP_OK) streams.push_back(i);
+    if (streams.empty()) return GAMUT_HIP_OK;
+    static thread_local PerDevice<DeviceScratch> verdict_dev_pd;
+    b.d_verdict = (uint32_t*)verdict_dev_pd.cur().get(streams.size() * 8);
+    if (!b.d_verdict) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: verdict table allocation failed");
+    SliceOverrides ov;
+    if (const char* v = getenv("GAMUT_HIP_PNG_SLICE_KB")) { const long kb = atol(v); if (kb >= 64 && kb <= (1 << 20)) ov.slice = (uint32_t)kb << 10; }      // (tuning)
+    if (const char* v = getenv("GAMUT_HIP_PNG_PITCHED")) ov.pitched = atoi(v) != 0;                            // (measurements)
+    b.plan = plan_slices(b.idat_len, b.slot_bytes, streams, ov);
+    static thread_local PerDevice<PinnedScratch> blob_pinned_pd;
+    static thread_local PerDevice<DeviceScratch> blob_dev_pd;
+    b.h_blob = blob_pinned_pd.cur().get(b.plan.blob_bytes + 16);
+    b.d_blob = (uint8_t*)blob_dev_pd.cur().get(b.plan.blob_bytes + 16);
+    if (!b.h_blob || !b.d_blob) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: staging for %llu bytes of IDAT data failed", (unsigned long long)b.plan.blob_bytes);
+    static thread_local PerDevice<hipStream_t> copy2_pd;
+    hipStream_t& copy_stream2 = copy2_pd.cur();
+    if (!copy_stream2 && hipStreamCreateWithFlags(&copy_stream2, hipStreamNonBlocking) != hipSuccess) return set_error(GAMUT_HIP_ERR_HIP, "png: stream creation failed");
+    b.copy_stream2 = copy_stream2;
+    b.drain.add(b.copy_stream2);
+    b.round_done = std::vector<std::atomic<int>>((size_t)b.plan.rounds);
+    for (auto& a : b.round_done) a.store(0);
+    return GAMUT_HIP_OK;
+}
+
+// The upload threads: a unit is slice r of one stream, gathered from the file's IDAT chunks into the pinned image; tight layout: and
+// queued for upload at once, on the two copy streams in turn
+void upload_worker(PngBatch& b)
+{
+    (void)hipSetDevice(b.dev);
+    const SlicePlan& p = b.plan;
+    for (size_t u; (u = b.next_unit.fetch_add(1, std::memory_order_relaxed)) < p.units.size(); ) {
+        const int r = p.units[u].first, k = p.units[u].second, i = p.who[(size_t)k];
+        const uint64_t lo = (uint64_t)r * p.slice, hi = p.avail(r, (size_t)k);        // the unit's bytes of the stream
+        uint8_t* const dst = b.h_blob + p.blob_off[(size_t)i] + lo;
+        copy_idat_range(b.segments[(size_t)i], b.idat_skip[(size_t)i], lo, hi, dst);
+        if (!p.pitched && hi > lo && hipMemcpyAsync(b.d_blob + p.blob_off[(size_t)i] + lo, dst, (size_t)(hi - lo), hipMemcpyHostToDevice, (u & 1) ? b.copy_stream2 : b.copy_stream) != hipSuccess) {
+            (void)hipGetLastError(); b.upload_failed.store(true);
+        }
+        b.round_done[(size_t)r].fetch_add(1, std::memory_order_release);
+    }
+}
+
+// Round r of the launch loop.  Once slice r of every stream is in the pinned image (pitched: it goes up now, in one copy) / has been
+// queued on the copy streams, the compute stream waits for it, then inflates what is there.
+int launch_round(PngBatch& b, int r)
+{
+    const SlicePlan& p = b.plan;
+    const size_t n = p.who.size(); const int active = p.units_in_round[(size_t)r];
+    while (b.round_done[(size_t)r].load(std::memory_order_acquire) < active) std::this_thread::yield();
+    if (p.pitched && active > 0 &&
+        hipMemcpy2DAsync(b.d_blob + (uint64_t)r * p.slice, p.pitch, b.h_blob + (uint64_t)r * p.slice, p.pitch, p.slice, (size_t)active, hipMemcpyHostToDevice, b.copy_stream) != hipSuccess) {
+        (void)hipGetLastError(); return set_error(GAMUT_HIP_ERR_HIP, "png: upload of slice %d failed", r);
+    }
+    if (!b.events.chain(b.copy_stream, b.st) || (!p.pitched && !b.events.chain(b.copy_stream2, b.st))) {
+        (void)hipGetLastError(); return set_error(GAMUT_HIP_ERR_HIP, "png: event for slice %d failed", r);
+    }
+    std::vector<uint32_t>& avail = b.avail[(size_t)r];
+    avail.resize(n);
+    for (size_t k = 0; k < n; ++k) avail[k] = p.avail(r, k);
+    return inflate_sliced_step((int)n, avail.data(), b.d_verdict, b.d_verdict + n, b.st);
+}
+
+// Device inflate, step two: the IDAT bytes go up slice by slice on the upload threads and the inflate kernel is launched once per slice
+// behind them (inflate_sliced_*: a stream stops where the bytes it may read end and goes on in the next launch).  A stream inflates at
+// ~150-600 MB/s, all of them side by side: about what PCIe delivers to all of them together, so the upload hides behind the kernel
+// instead of standing in front of it.  Returns once every stream of the call has been waited for.
+int launch_slices(PngBatch& b)
+{
+    const SlicePlan& p = b.plan;
+    const size_t n = p.who.size();
+    std::vector<gamut_hip_inflate_desc> descs;
+    for (int i : p.who) descs.push_back(gamut_hip_inflate_desc{ b.d_blob + p.blob_off[(size_t)i], b.d_arena + b.slot[(size_t)i], b.idat_len[(size_t)i], (uint32_t)b.slot_bytes[(size_t)i] });
+    b.verdict.resize(n * 2); b.avail.resize((size_t)p.rounds);
+    if (int rc = inflate_sliced_begin(descs.data(), (int)n, b.st)) return rc;
+    HostThreads pool;
+    if (pool.start(b.threads, [&b] { upload_worker(b); }) == 0) upload_worker(b);      // (no thread could be started: this one does it all, then launches)
+    int launch_rc = GAMUT_HIP_OK;
+    for (int r = 0; r < p.rounds && launch_rc == GAMUT_HIP_OK; ++r) launch_rc = launch_round(b, r);
+    pool.join();
+    if (launch_rc == GAMUT_HIP_OK && b.upload_failed.load()) launch_rc = set_error(GAMUT_HIP_ERR_HIP, "png: upload of the IDAT data failed");
+    if (launch_rc == GAMUT_HIP_OK && hipMemcpyAsync(b.verdict.data(), b.d_verdict, n * 8, hipMemcpyDeviceToHost, b.st) != hipSuccess) launch_rc = set_error(GAMUT_HIP_ERR_HIP, "png: verdict download failed");
+    const hipError_t sync_rc = hipStreamSynchronize(b.st);
+    (void)hipStreamSynchronize(b.copy_stream); (void)hipStreamSynchronize(b.copy_stream2);
+    b.events.destroy();
+    if (launch_rc != GAMUT_HIP_OK) return launch_rc;
+    if (sync_rc != hipSuccess) return set_error(GAMUT_HIP_ERR_HIP, "png: inflate on the device failed: %s", hipGetErrorString(sync_rc));
+    return GAMUT_HIP_OK;
+}
+
+// what the inflate kernel made of every stream: its length in the arena, or a damaged stream
+void collect_verdicts(PngBatch& b)
+{
+    const size_t n = b.plan.who.size();
+    for (size_t k = 0; k < n; ++k) {
+        const int i = b.plan.who[k];
+        BatchFile& f = b.files[(size_t)i];
+        if (b.verdict[n + k]) { f.fail(i, GAMUT_HIP_ERR_DECODE, "png: corrupt zlib stream"); continue; }
+        f.raw_len = b.verdict[k];
+        f.uploaded = true;
+        f.batched = batched(f, b.req_comp, b.bits);
+    }
+}
+
+int inflate_on_device(PngBatch& b)
+{
+    const TracePoint t_inf = trace_now();
+    if (int rc = plan_device_inflate(b)) return rc;
+    if (!b.plan.who.empty()) {
+        if (int rc = launch_slices(b)) return rc;
+        collect_verdicts(b);
+    }
+    b.ms_device_inflate = ms_since(t_inf);
+    return GAMUT_HIP_OK;
+}
+
+// the batched files by geometry, in the order of their launches: where each one's stream lies in the arena and where its pixels go.
+// aligned / lines: every image on a dword / on a 128-byte line of memory
+void group_by_geometry(PngBatch& b, bool& aligned, bool& lines)
+{
+    aligned = ((uintptr_t)b.out % 4) == 0; lines = ((uintptr_t)b.out % 128) == 0;
+    for (int i = 0; i < b.count; ++i) {
+        const BatchFile& f = b.files[(size_t)i];
+        if (!f.batched) continue;
+        b.groups[std::make_tuple(f.h.x, f.h.y, f.h.img_n, f.out_n, f.h.depth, f.h.color)].push_back(i);
+        aligned = aligned && (b.out_offset[i] % 4) == 0;
+        lines = lines && (b.out_offset[i] % 128) == 0;
+        ++b.n_batched;
+    }
+    const size_t nb = (size_t)b.n_batched;
+    b.status.assign(nb, 0); b.offs.resize(nb * 2); b.order.reserve(nb);
+    for (auto& g : b.groups) for (int i : g.second) { b.offs[b.order.size()] = b.slot[(size_t)i]; b.offs[nb + b.order.size()] = b.out_offset[i]; b.order.push_back(i); }
+}
+
+// one de-filter launch per geometry
+int defilter_batched(PngBatch& b)
+{
+    bool aligned, lines;
+    group_by_geometry(b, aligned, lines);
+    if (!b.n_batched) return GAMUT_HIP_OK;
+    const size_t nb = (size_t)b.n_batched, o_status = nb * 16;
+    static thread_local PerDevice<DeviceScratch> tables_pd;
+    uint8_t* d_tab = (uint8_t*)tables_pd.cur().get(o_status + nb * 4);
+    if (!d_tab) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: table allocation failed");
+    GAMUT_HIP_CHECK(hipMemcpyAsync(d_tab, b.offs.data(), b.offs.size() * 8, hipMemcpyHostToDevice, b.st));
+    GAMUT_HIP_CHECK(hipMemsetAsync(d_tab + o_status, 0, nb * 4, b.st));
+    size_t base = 0; int launch_rc = GAMUT_HIP_OK;
+    for (auto& g : b.groups) {
+        const BatchFile& f = b.files[(size_t)g.second[0]];
+        const int n = (int)g.second.size();
+        const int rc = png_defilter_launch(b.d_arena, 0, f.need, b.out, 0, f.h.x, f.h.y, f.h.img_n, f.out_n, f.h.depth, f.h.color, n,
+                                           (uint32_t*)(d_tab + o_status) + base, b.st,
+                                           (const int64_t*)d_tab + base, (const int64_t*)d_tab + nb + base, aligned, lines);
+        if (rc != GAMUT_HIP_OK && launch_rc == GAMUT_HIP_OK) {
+            launch_rc = rc;
+            for (int i : g.second) b.files[(size_t)i].fail(i, rc, last_error_buf());
+        }
+        base += (size_t)n;
+    }
+    GAMUT_HIP_CHECK(hipMemcpyAsync(b.status.data(), d_tab + o_status, nb * 4, hipMemcpyDeviceToHost, b.st));
+    GAMUT_HIP_CHECK(hipStreamSynchronize(b.st));
+    for (size_t k = 0; k < b.order.size(); ++k) {
+        BatchFile& f = b.files[(size_t)b.order[k]];
+        if (b.status[k] && f.rc == GAMUT_HIP_OK) f.fail(b.order[k], GAMUT_HIP_ERR_DECODE, "png: invalid filter");
+    }
+    return GAMUT_HIP_OK;
+}
+
+// the others (interlaced, palette, tRNS, channel or depth conversion): the whole of stbi__do_png per file, from the arena
+void decode_remaining(PngBatch& b)
+{
+    for (int i = 0; i < b.count; ++i) {
+        BatchFile& f = b.files[(size_t)i];
+        if (f.rc != GAMUT_HIP_OK || !f.uploaded || f.batched) continue;
+        int w = 0, hh = 0, n = 0, bits = 8;
+        if (png_run(f.h, nullptr, f.raw_len, b.req_comp, b.bits, b.out + b.out_offset[i], &w, &hh, &n, &bits, b.st, b.d_arena + b.slot[(size_t)i])) { f.channels_in_file = n; f.bits = bits; }
+        else f.fail(i, GAMUT_HIP_ERR_DECODE, last_error_buf());
+    }
+    clear_error();
+}
+
+// the results: info and status per file; the call's verdict is the first failing file's
+int report(PngBatch& b)
+{
+    if (b.trace && b.device_inflate) fprintf(stderr, "[gamut_hip] png_decode_batch_device: inflate on the device: upload + kernel + verdicts %.1f ms\n", b.ms_device_inflate);
+    if (b.trace) fprintf(stderr, "[gamut_hip] png_decode_batch_device: %d files on %d threads: workers %.1f ms (per file: chunk walk + inflate %.1f ms, upload + wait %.1f ms), GPU stages %.1f ms (%d files in %d batched launches)\n",
+                         b.count, b.threads, b.ms_workers, b.us_inflate.load() / 1000.0 / b.count, b.us_upload.load() / 1000.0 / b.count, ms_since(b.t_begin) - b.ms_workers, b.n_batched, (int)b.groups.size());
+    const BatchFile* first = nullptr;
+    for (int i = 0; i < b.count; ++i) {
+        const BatchFile& f = b.files[(size_t)i];
+        gamut_hip_png_info& info = b.info[i];
+        memset(&info, 0, sizeof(info));
+        if (f.rc == GAMUT_HIP_OK) {
+            info.width = f.h.x; info.height = f.h.y; info.channels_in_file = f.channels_in_file;
+            info.channels = b.req_comp ? b.req_comp : f.channels_in_file; info.bits = f.bits;
+            info.pixels_per_meter_x = f.h.ppmX; info.pixels_per_meter_y = f.h.ppmY; info.pixel_aspect_ratio = f.h.aspect;
+        }
+        if (b.status_host) b.status_host[i] = f.rc;
+        if (f.rc != GAMUT_HIP_OK && !first) first = &f;
+    }
+    return first ? set_error(first->rc, "%s", first->msg) : GAMUT_HIP_OK;
+}
 
 } // namespace
 } // namespace gamut
@@ -407,11 +571,7 @@ uint16_t* gamut_hip_stbi_load_16_from_memory(const uint8_t* data, size_t len, in
     return (uint16_t*)r;
 }
 
-// Batch: chunk walk + inflate on host threads, one file per thread at a time, into pinned memory; the inflated stream goes
-// to a device arena at once (copy stream).  Files that need nothing but de-filter + expand -- not interlaced, no palette,
-// no tRNS, channel count and depth as asked -- are then de-filtered TOGETHER, one launch per geometry with one workgroup per
-// image (a 4K image alone occupies one CU for 4.5 ms; 64 of them side by side take about as long).  The others run the
-// whole of stbi__do_png on their worker's own stream right away.
+// files -> pixels in device memory (PngBatch above: the stages and what they share)
 int gamut_hip_png_decode_batch_device(const uint8_t* const* data, const size_t* len, int count, int req_comp, int bits,
                                       const int64_t* out_offset, uint8_t* out, gamut_hip_png_info* info, int* status_host,
                                       int threads, void* stream)
@@ -421,336 +581,18 @@ int gamut_hip_png_decode_batch_device(const uint8_t* const* data, const size_t* 
         return set_error(GAMUT_HIP_ERR_INVALID_ARG, "png_decode_batch_device: bad arguments");
     if (count == 0) return GAMUT_HIP_OK;
     if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
     try {
         if (threads <= 0) threads = host_threads();
         threads = threads < 1 ? 1 : threads > count ? count : threads;
-        hipStream_t st = pick_stream(stream);
-        static thread_local PerDevice<hipStream_t> copy_stream_pd;
-        hipStream_t& copy_stream_tl = copy_stream_pd.cur();
-        if (!copy_stream_tl) GAMUT_HIP_CHECK(hipStreamCreateWithFlags(&copy_stream_tl, hipStreamNonBlocking));
-        // a plain local: thread_local variables are not captured by the worker lambda below -- every worker thread would
-        // read ITS OWN (null) instance and upload on the legacy null stream
-        const hipStream_t copy_stream = copy_stream_tl;
-
-        // 0. IHDR of every file: a slot in the device arena for its inflated stream
-        std::vector<BatchFile> files((size_t)count);
-        std::vector<int64_t> slot((size_t)count, -1), slot_bytes((size_t)count, 0);
-        int64_t arena_bytes = 0;
-        for (int i = 0; i < count; ++i) {
-            PngHeader h;
-            if (parse(data[i], len[i], h, true)) continue;                       // the worker reports the error
-            const uint64_t wb = ((uint64_t)h.img_n * h.x * (uint32_t)h.depth + 7) >> 3, room = (wb + 8) * h.y + 64;      // Adam7: <= 15/8 y rows, each with a filter byte and a rounded-up last byte
-            if (room > 0xFFFFFF00ull) continue;
-            slot[(size_t)i] = arena_bytes; slot_bytes[(size_t)i] = (int64_t)room; arena_bytes += (int64_t)((room + 255) & ~(uint64_t)255);
-        }
-        clear_error();
-        static thread_local PerDevice<DeviceScratch> arena_pd;
-        DeviceScratch& arena = arena_pd.cur();
-        uint8_t* d_arena = arena_bytes ? (uint8_t*)arena.get((size_t)arena_bytes, st) : nullptr;
-        if (arena_bytes && !d_arena) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: device arena of %lld bytes failed", (long long)arena_bytes);
-
-        // 1. workers: chunk walk + inflate into the worker's pinned buffer, stream to the arena
-        const bool trace = getenv("GAMUT_HIP_TRACE") != nullptr;
-        const auto t_begin = std::chrono::steady_clock::now();
-        auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-        std::atomic<int64_t> us_inflate{ 0 }, us_upload{ 0 };
-        std::atomic<int> next{ 0 };
-        // Inflate on the GPU (inflate.hip) when the batch is large enough to beat the host threads: the workers then only
-        // walk the chunks and gather the IDAT bytes into one pinned upload image (file i's share starts at blob_off[i]; its
-        // IDAT bytes cannot outnumber the file's own).  GAMUT_HIP_PNG_INFLATE=host / device overrides the choice.
-        bool device_inflate = count > threads;                   // (threads <= count here)
-        if (const char* v = getenv("GAMUT_HIP_PNG_INFLATE")) device_inflate = strcmp(v, "device") == 0 ? true : strcmp(v, "host") == 0 ? false : device_inflate;
-        std::vector<size_t> blob_off((size_t)count + 1, 0);
-        std::vector<uint32_t> idat_len((size_t)count, 0), idat_skip((size_t)count, 0);
-        uint8_t* h_blob = nullptr; uint8_t* d_blob = nullptr;
-        static thread_local PerDevice<PinnedScratch> blob_pinned_pd;
-        static thread_local PerDevice<DeviceScratch> blob_dev_pd;
-        PinnedScratch& blob_pinned = blob_pinned_pd.cur(); DeviceScratch& blob_dev = blob_dev_pd.cur();
-        // Device inflate, step one: the chunk walk of every file (no byte of IDAT data is touched: parse() notes where the payloads are).
-        std::vector<std::vector<std::pair<const uint8_t*, uint32_t>>> segments(device_inflate ? (size_t)count : 0);
-        auto gather = [&]() {
-            (void)hipSetDevice(dev);
-            for (int i; (i = next.fetch_add(1, std::memory_order_relaxed)) < count; ) {
-                BatchFile& f = files[(size_t)i];
-                PngHeader h;
-                h.idat_segments = &segments[(size_t)i];
-                const auto t_in = std::chrono::steady_clock::now();
-                int rc = parse(data[i], len[i], h, false);
-                if (rc == GAMUT_HIP_OK && !h.seen_idat) rc = set_error(GAMUT_HIP_ERR_DECODE, "png: no IDAT");
-                uint32_t skip = 0;
-                if (rc == GAMUT_HIP_OK && !h.is_iphone) {                       // the zlib header, as inflate_idat checks it (stbdec.d:1281-1290)
-                    uint8_t b[2] = { 0, 0 }; uint32_t got = 0;
-                    for (const auto& sg : segments[(size_t)i]) for (uint32_t k = 0; k < sg.second && got < 2; ++k) b[got++] = sg.first[k];
-                    if (h.ioff < 2 || ((b[0] * 256 + b[1]) % 31) != 0 || (b[1] & 32) || (b[0] & 15) != 8) rc = set_error(GAMUT_HIP_ERR_DECODE, "png: bad zlib header");
-                    skip = 2;
-                }
-                if (rc == GAMUT_HIP_OK && slot[(size_t)i] < 0) rc = set_error(GAMUT_HIP_ERR_DECODE, "png: image too large");
-                if (rc != GAMUT_HIP_OK) { f.rc = rc; snprintf(f.msg, sizeof(f.msg), "image %d: %s", i, last_error_buf()); continue; }
-                idat_len[(size_t)i] = h.ioff - skip;
-                idat_skip[(size_t)i] = skip;
-                h.idat_segments = nullptr;
-                f.h = h;
-                f.out_n = h.img_n;
-                if ((req_comp == h.img_n + 1 && req_comp != 3 && !h.pal_img_n) || h.has_trans) f.out_n = h.img_n + 1;      // stbdec.d:1821-1824
-                f.bits = h.depth <= 8 ? 8 : 16; f.channels_in_file = h.img_n;
-                const uint64_t wb = ((uint64_t)h.img_n * h.x * (uint32_t)h.depth + 7) >> 3;
-                f.need = (uint32_t)((wb + 1) * h.y);
-                us_inflate += (int64_t)(ms_since(t_in) * 1000);
-            }
-        };
-        auto work = [&]() {
-            (void)hipSetDevice(dev);
-            HostBuf buf = pinned_pool().take();
-            hipEvent_t copied = nullptr;
-            (void)hipEventCreateWithFlags(&copied, hipEventDisableTiming);
-            for (int i; (i = next.fetch_add(1, std::memory_order_relaxed)) < count; ) {
-                BatchFile& f = files[(size_t)i];
-                PngJob j; j.raw = buf;                                           // borrow the worker's pinned buffer
-                const auto t_in = std::chrono::steady_clock::now();
-                const int rc = png_prepare(data[i], len[i], j);
-                buf = j.raw; j.raw = HostBuf{};
-                us_inflate += (int64_t)(ms_since(t_in) * 1000);
-                if (rc != GAMUT_HIP_OK) { f.rc = rc; snprintf(f.msg, sizeof(f.msg), "image %d: %s", i, last_error_buf()); continue; }
-                free(j.h.idata); j.h.idata = nullptr;
-                f.h = j.h;
-                const PngHeader& h = f.h;
-                f.out_n = h.img_n;
-                if ((req_comp == h.img_n + 1 && req_comp != 3 && !h.pal_img_n) || h.has_trans) f.out_n = h.img_n + 1;      // stbdec.d:1821-1824
-                f.bits = h.depth <= 8 ? 8 : 16; f.channels_in_file = h.img_n;
-                const uint64_t wb = ((uint64_t)h.img_n * h.x * (uint32_t)h.depth + 7) >> 3, need = (wb + 1) * h.y;
-                f.need = (uint32_t)need;
-                if (slot[(size_t)i] < 0 || !copied) { f.rc = GAMUT_HIP_ERR_DECODE; snprintf(f.msg, sizeof(f.msg), "image %d: png: image too large", i); continue; }
-                f.raw_len = (uint32_t)((int64_t)j.raw_len < slot_bytes[(size_t)i] ? (int64_t)j.raw_len : slot_bytes[(size_t)i]);
-                const auto t_upl = std::chrono::steady_clock::now();
-                if (hipMemcpyAsync(d_arena + slot[(size_t)i], buf.p, f.raw_len, hipMemcpyHostToDevice, copy_stream) != hipSuccess ||
-                    hipEventRecord(copied, copy_stream) != hipSuccess || hipEventSynchronize(copied) != hipSuccess) {
-                    f.rc = GAMUT_HIP_ERR_HIP; snprintf(f.msg, sizeof(f.msg), "image %d: png: upload failed", i); continue;
-                }
-                us_upload += (int64_t)(ms_since(t_upl) * 1000);
-                f.uploaded = true;
-                f.batched = !h.interlace && !h.has_trans && !h.pal_img_n && (req_comp == 0 || req_comp == f.out_n) && (bits == 0 || bits == f.bits) && f.raw_len >= need;
-            }
-            if (copied) (void)hipEventDestroy(copied);
-            pinned_pool().give(buf);
-        };
-        {
-            std::vector<std::thread> pool;
-            if (device_inflate) {
-                try { for (int t = 1; t < threads; ++t) pool.emplace_back(gather); } catch (...) {}
-                gather();
-            } else {
-                try { for (int t = 1; t < threads; ++t) pool.emplace_back(work); } catch (...) {}
-                work();
-            }
-            for (std::thread& th : pool) th.join();
-        }
-        clear_error();
-        GAMUT_HIP_CHECK(hipStreamSynchronize(copy_stream));                       // (every worker waited for its own copies already)
-        double ms_device_inflate = 0;
-        if (device_inflate) {
-            // Step two: the IDAT bytes go up SLICE BY SLICE -- slice r of every stream, then slice r + 1 of every stream -- and the inflate
-            // kernel is launched once per slice behind them (inflate_sliced_*: a stream stops where the bytes it may read end and goes on
-            // in the next launch).  A stream inflates at ~150-600 MB/s, all of them side by side: about what PCIe delivers to all of them
-            // together, so the upload hides behind the kernel instead of standing in front of it.
-            const auto t_inf = std::chrono::steady_clock::now();
-            std::vector<gamut_hip_inflate_desc> descs; std::vector<int> who;
-            uint32_t longest = 0;
-            for (int i = 0; i < count; ++i) if (files[(size_t)i].rc == GAMUT_HIP_OK) who.push_back(i);
-            // longest streams first: a stream is one workgroup for its whole length, and workgroups start in the order of the list -- with
-            // more streams than compute units the long ones must not be the ones that start last
-            std::stable_sort(who.begin(), who.end(), [&](int a, int b) { return idat_len[(size_t)a] > idat_len[(size_t)b]; });
-            for (int i : who) longest = idat_len[(size_t)i] > longest ? idat_len[(size_t)i] : longest;
-            if (!who.empty()) {
-                const size_t n = who.size();
-                static thread_local PerDevice<DeviceScratch> verdict_dev_pd;
-                DeviceScratch& verdict_dev = verdict_dev_pd.cur();
-                uint32_t* d_verdict = (uint32_t*)verdict_dev.get(n * 8);
-                if (!d_verdict) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: verdict table allocation failed");
-                std::vector<uint32_t> verdict(n * 2);
-                // 1 MiB slices; 512 KiB for up to 256 well-compressed large images, where a stream inflates more slowly than it arrives
-                // (measured, 256 files: 4K of 12 MB 100 ms with 1 MiB slices, 127 with 512 KiB; 4K of 3.6 MB 60 / 57 ms; 1080p of 3.1 MB
-                // 33 / 36 ms; 1024 files of 1080p 118 / 132 ms); at most 32 launches
-                int64_t largest_out = 0;
-                for (int i : who) largest_out = std::max(largest_out, slot_bytes[(size_t)i]);
-                uint32_t slice = (longest < (8u << 20) && n <= 256 && largest_out >= (16 << 20)) ? 1u << 19 : 1u << 20;
-                if (const char* v = getenv("GAMUT_HIP_PNG_SLICE_KB")) { const long kb = atol(v); if (kb >= 64 && kb <= (1 << 20)) slice = (uint32_t)kb << 10; }      // (tuning)
-                while ((uint64_t)slice * 32u < longest) slice *= 2;
-                const int rounds = longest ? (int)(((uint64_t)longest + slice - 1) / slice) : 1;
-                // The staging image.  One copy per (stream, slice) is a megabyte at a time: 37 GB/s on one copy stream where the link does 57
-                // (tools/microbench/h2d_streams.hip, profiles/r04_h2d_streams.txt).  With every stream's share `pitch` bytes apart -- the
-                // streams in the order of the list, longest first, so that those still running in a round are a prefix -- slice r of all of
-                // them is ONE pitched copy (hipMemcpy2DAsync: 57 GB/s even with 512 KiB rows).  Batches of very unequal streams (the pitched
-                // image would be more than twice the data) keep their tight layout and piece-wise copies, spread over two copy streams (46 GB/s).
-                uint64_t data_bytes = 0;
-                for (int i : who) data_bytes += ((uint64_t)idat_len[(size_t)i] + 15) & ~(uint64_t)15;
-                const uint64_t pitch = (uint64_t)rounds * slice;
-                bool pitched = pitch * n <= 2 * data_bytes + (64u << 20);
-                if (const char* v = getenv("GAMUT_HIP_PNG_PITCHED")) pitched = atoi(v) != 0;                           // (measurements)
-                const uint64_t blob_bytes = pitched ? pitch * n : data_bytes;
-                h_blob = blob_pinned.get(blob_bytes + 16);
-                d_blob = (uint8_t*)blob_dev.get(blob_bytes + 16);
-                if (!h_blob || !d_blob) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: staging for %llu bytes of IDAT data failed", (unsigned long long)blob_bytes);
-                {
-                    uint64_t at = 0;
-                    for (size_t k = 0; k < n; ++k) { const int i = who[k]; blob_off[(size_t)i] = pitched ? k * pitch : at; at += ((uint64_t)idat_len[(size_t)i] + 15) & ~(uint64_t)15; }
-                }
-                for (int i : who) descs.push_back(gamut_hip_inflate_desc{ d_blob + blob_off[(size_t)i], d_arena + slot[(size_t)i], idat_len[(size_t)i], (uint32_t)slot_bytes[(size_t)i] });
-                static thread_local PerDevice<hipStream_t> copy2_pd;
-                hipStream_t& copy_stream2 = copy2_pd.cur();
-                if (!copy_stream2 && hipStreamCreateWithFlags(&copy_stream2, hipStreamNonBlocking) != hipSuccess) return set_error(GAMUT_HIP_ERR_HIP, "png: stream creation failed");
-                // the units of work, slice-major: (round, stream)
-                std::vector<std::pair<int, int>> units;
-                std::vector<int> units_in_round((size_t)rounds, 0);
-                for (int r = 0; r < rounds; ++r)
-                    for (size_t k = 0; k < n; ++k) if ((uint64_t)r * slice < idat_len[(size_t)who[k]] || (r == 0 && idat_len[(size_t)who[k]] == 0)) { units.emplace_back(r, (int)k); ++units_in_round[(size_t)r]; }
-                std::vector<std::atomic<int>> round_done((size_t)rounds);
-                for (auto& a : round_done) a.store(0);
-                std::atomic<size_t> next_unit{ 0 };
-                std::atomic<bool> upload_failed{ false };
-                auto upload = [&]() {
-                    (void)hipSetDevice(dev);
-                    for (size_t u; (u = next_unit.fetch_add(1, std::memory_order_relaxed)) < units.size(); ) {
-                        const int r = units[u].first, i = who[(size_t)units[u].second];
-                        const uint64_t lo = (uint64_t)r * slice, hi = std::min<uint64_t>(lo + slice, idat_len[(size_t)i]);
-                        // bytes [lo, hi) of the stream = bytes [lo + skip, hi + skip) of the concatenated IDAT payloads
-                        uint8_t* dst = h_blob + blob_off[(size_t)i] + lo;
-                        uint64_t at = 0, want_lo = lo + idat_skip[(size_t)i], want_hi = hi + idat_skip[(size_t)i];
-                        for (const auto& sg : segments[(size_t)i]) {
-                            const uint64_t s_lo = at, s_hi = at + sg.second;
-                            at = s_hi;
-                            if (s_hi <= want_lo) continue;
-                            if (s_lo >= want_hi) break;
-                            const uint64_t c_lo = std::max(s_lo, want_lo), c_hi = std::min(s_hi, want_hi);
-                            memcpy(dst + (c_lo - want_lo), sg.first + (c_lo - s_lo), (size_t)(c_hi - c_lo));
-                        }
-                        if (!pitched && hi > lo && hipMemcpyAsync(d_blob + blob_off[(size_t)i] + lo, dst, (size_t)(hi - lo), hipMemcpyHostToDevice, (u & 1) ? copy_stream2 : copy_stream) != hipSuccess) {
-                            (void)hipGetLastError(); upload_failed.store(true);
-                        }
-                        round_done[(size_t)r].fetch_add(1, std::memory_order_release);
-                    }
-                };
-                if (int rc = inflate_sliced_begin(descs.data(), (int)n, st)) return rc;
-                std::vector<std::thread> pool;
-                try { for (int t = 0; t < threads; ++t) pool.emplace_back(upload); } catch (...) {}
-                if (pool.empty()) upload();                                       // (no thread could be started: this one does it all, then launches)
-                std::vector<hipEvent_t> up((size_t)rounds, nullptr);
-                std::vector<std::vector<uint32_t>> avail((size_t)rounds);          // (one table per launch, alive until the stream has been waited for)
-                int launch_rc = GAMUT_HIP_OK;
-                for (int r = 0; r < rounds && launch_rc == GAMUT_HIP_OK; ++r) {
-                    while (round_done[(size_t)r].load(std::memory_order_acquire) < units_in_round[(size_t)r]) std::this_thread::yield();
-                    // slice r of every stream is in the pinned image (pitched: it goes up now, in one copy) / has been queued on the copy streams:
-                    // the compute stream waits for it, then inflates what is there
-                    if (pitched && units_in_round[(size_t)r] > 0 &&
-                        hipMemcpy2DAsync(d_blob + (uint64_t)r * slice, pitch, h_blob + (uint64_t)r * slice, pitch, slice, (size_t)units_in_round[(size_t)r], hipMemcpyHostToDevice, copy_stream) != hipSuccess) {
-                        (void)hipGetLastError(); launch_rc = set_error(GAMUT_HIP_ERR_HIP, "png: upload of slice %d failed", r); break;
-                    }
-                    if (hipEventCreateWithFlags(&up[(size_t)r], hipEventDisableTiming) != hipSuccess || hipEventRecord(up[(size_t)r], copy_stream) != hipSuccess ||
-                        hipStreamWaitEvent(st, up[(size_t)r], 0) != hipSuccess) { (void)hipGetLastError(); launch_rc = set_error(GAMUT_HIP_ERR_HIP, "png: event for slice %d failed", r); break; }
-                    if (!pitched) {
-                        hipEvent_t e2 = nullptr;
-                        if (hipEventCreateWithFlags(&e2, hipEventDisableTiming) != hipSuccess || hipEventRecord(e2, copy_stream2) != hipSuccess || hipStreamWaitEvent(st, e2, 0) != hipSuccess) {
-                            (void)hipGetLastError(); launch_rc = set_error(GAMUT_HIP_ERR_HIP, "png: event for slice %d failed", r); break; }
-                        up.push_back(e2);
-                    }
-                    avail[(size_t)r].resize(n);
-                    for (size_t k = 0; k < n; ++k) avail[(size_t)r][k] = (uint32_t)std::min<uint64_t>((uint64_t)(r + 1) * slice, idat_len[(size_t)who[k]]);
-                    launch_rc = inflate_sliced_step((int)n, avail[(size_t)r].data(), d_verdict, d_verdict + n, st);
-                }
-                for (std::thread& th : pool) th.join();
-                if (launch_rc == GAMUT_HIP_OK && upload_failed.load()) launch_rc = set_error(GAMUT_HIP_ERR_HIP, "png: upload of the IDAT data failed");
-                if (launch_rc == GAMUT_HIP_OK && hipMemcpyAsync(verdict.data(), d_verdict, n * 8, hipMemcpyDeviceToHost, st) != hipSuccess) launch_rc = set_error(GAMUT_HIP_ERR_HIP, "png: verdict download failed");
-                const hipError_t sync_rc = hipStreamSynchronize(st);
-                (void)hipStreamSynchronize(copy_stream); (void)hipStreamSynchronize(copy_stream2);
-                for (hipEvent_t e : up) if (e) (void)hipEventDestroy(e);
-                if (launch_rc != GAMUT_HIP_OK) return launch_rc;
-                if (sync_rc != hipSuccess) return set_error(GAMUT_HIP_ERR_HIP, "png: inflate on the device failed: %s", hipGetErrorString(sync_rc));
-                for (size_t k = 0; k < n; ++k) {
-                    BatchFile& f = files[(size_t)who[k]];
-                    if (verdict[n + k]) { f.rc = GAMUT_HIP_ERR_DECODE; snprintf(f.msg, sizeof(f.msg), "image %d: png: corrupt zlib stream", who[k]); continue; }
-                    const PngHeader& h = f.h;
-                    f.raw_len = verdict[k];
-                    f.uploaded = true;
-                    f.batched = !h.interlace && !h.has_trans && !h.pal_img_n && (req_comp == 0 || req_comp == f.out_n) && (bits == 0 || bits == f.bits) && f.raw_len >= f.need;
-                }
-            }
-            ms_device_inflate = ms_since(t_inf);
-        }
-        const double ms_workers = ms_since(t_begin);
-
-        // 2. one de-filter launch per geometry
-        std::map<std::tuple<uint32_t, uint32_t, int, int, int, int>, std::vector<int>> groups;
-        bool aligned = ((uintptr_t)out % 4) == 0, lines = ((uintptr_t)out % 128) == 0;       // every image on a dword / on a 128-byte line of memory
-        int n_batched = 0;
-        for (int i = 0; i < count; ++i) {
-            const BatchFile& f = files[(size_t)i];
-            if (!f.batched) continue;
-            groups[std::make_tuple(f.h.x, f.h.y, f.h.img_n, f.out_n, f.h.depth, f.h.color)].push_back(i);
-            aligned = aligned && (out_offset[i] % 4) == 0;
-            lines = lines && (out_offset[i] % 128) == 0;
-            ++n_batched;
-        }
-        std::vector<uint32_t> status((size_t)n_batched, 0);
-        std::vector<int> order; order.reserve((size_t)n_batched);
-        int launch_rc = GAMUT_HIP_OK;
-        if (n_batched) {
-            std::vector<int64_t> offs((size_t)n_batched * 2);
-            for (auto& g : groups) for (int i : g.second) { offs[order.size()] = slot[(size_t)i]; offs[(size_t)n_batched + order.size()] = out_offset[i]; order.push_back(i); }
-            static thread_local PerDevice<DeviceScratch> tables_pd;
-            DeviceScratch& tables = tables_pd.cur();
-            const size_t o_status = (size_t)n_batched * 16;
-            uint8_t* d_tab = (uint8_t*)tables.get(o_status + (size_t)n_batched * 4);
-            if (!d_tab) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png: table allocation failed");
-            GAMUT_HIP_CHECK(hipMemcpyAsync(d_tab, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, st));
-            GAMUT_HIP_CHECK(hipMemsetAsync(d_tab + o_status, 0, (size_t)n_batched * 4, st));
-            size_t base = 0;
-            for (auto& g : groups) {
-                const BatchFile& f = files[(size_t)g.second[0]];
-                const int n = (int)g.second.size();
-                const int rc = png_defilter_launch(d_arena, 0, f.need, out, 0, f.h.x, f.h.y, f.h.img_n, f.out_n, f.h.depth, f.h.color, n,
-                                                   (uint32_t*)(d_tab + o_status) + base, st,
-                                                   (const int64_t*)d_tab + base, (const int64_t*)d_tab + n_batched + base, aligned, lines);
-                if (rc != GAMUT_HIP_OK && launch_rc == GAMUT_HIP_OK) {
-                    launch_rc = rc;
-                    for (int i : g.second) { files[(size_t)i].rc = rc; snprintf(files[(size_t)i].msg, sizeof(files[(size_t)i].msg), "image %d: %s", i, last_error_buf()); }
-                }
-                base += (size_t)n;
-            }
-            GAMUT_HIP_CHECK(hipMemcpyAsync(status.data(), d_tab + o_status, (size_t)n_batched * 4, hipMemcpyDeviceToHost, st));
-            GAMUT_HIP_CHECK(hipStreamSynchronize(st));
-            for (size_t k = 0; k < order.size(); ++k)
-                if (status[k] && files[(size_t)order[k]].rc == GAMUT_HIP_OK) {
-                    files[(size_t)order[k]].rc = GAMUT_HIP_ERR_DECODE; snprintf(files[(size_t)order[k]].msg, sizeof(files[(size_t)order[k]].msg), "image %d: png: invalid filter", order[k]);
-                }
-        }
-        // 3. the others (interlaced, palette, tRNS, channel or depth conversion): the whole of stbi__do_png per file, from the arena
-        for (int i = 0; i < count; ++i) {
-            BatchFile& f = files[(size_t)i];
-            if (f.rc != GAMUT_HIP_OK || !f.uploaded || f.batched) continue;
-            int w = 0, hh = 0, n = 0, b = 8;
-            if (png_run(f.h, nullptr, f.raw_len, req_comp, bits, out + out_offset[i], &w, &hh, &n, &b, st, d_arena + slot[(size_t)i])) { f.channels_in_file = n; f.bits = b; }
-            else { f.rc = GAMUT_HIP_ERR_DECODE; snprintf(f.msg, sizeof(f.msg), "image %d: %s", i, last_error_buf()); }
-        }
-        clear_error();
-        if (trace && device_inflate) fprintf(stderr, "[gamut_hip] png_decode_batch_device: inflate on the device: upload + kernel + verdicts %.1f ms\n", ms_device_inflate);
-        if (trace) fprintf(stderr, "[gamut_hip] png_decode_batch_device: %d files on %d threads: workers %.1f ms (per file: chunk walk + inflate %.1f ms, upload + wait %.1f ms), GPU stages %.1f ms (%d files in %d batched launches)\n",
-                           count, threads, ms_workers, us_inflate.load() / 1000.0 / count, us_upload.load() / 1000.0 / count, ms_since(t_begin) - ms_workers, n_batched, (int)groups.size());
-        // 4. results
-        int first = GAMUT_HIP_OK; char first_msg[200] = { 0 };
-        for (int i = 0; i < count; ++i) {
-            const BatchFile& f = files[(size_t)i];
-            memset(&info[i], 0, sizeof(info[i]));
-            if (f.rc == GAMUT_HIP_OK) {
-                info[i].width = f.h.x; info[i].height = f.h.y; info[i].channels_in_file = f.channels_in_file;
-                info[i].channels = req_comp ? req_comp : f.channels_in_file; info[i].bits = f.bits;
-                info[i].pixels_per_meter_x = f.h.ppmX; info[i].pixels_per_meter_y = f.h.ppmY; info[i].pixel_aspect_ratio = f.h.aspect;
-            }
-            if (status_host) status_host[i] = f.rc;
-            if (f.rc != GAMUT_HIP_OK && first == GAMUT_HIP_OK) { first = f.rc; snprintf(first_msg, sizeof(first_msg), "%s", f.msg); }
-        }
-        if (first != GAMUT_HIP_OK) return set_error(first, "%s", first_msg);
-        return GAMUT_HIP_OK;
+        PngBatch b{ data, len, count, req_comp, bits, out_offset, out, info, status_host, threads, pick_stream(stream) };
+        (void)hipGetDevice(&b.dev);
+        if (int rc = plan_arena(b)) return rc;
+        if (int rc = run_host_stage(b)) return rc;
+        if (b.device_inflate) if (int rc = inflate_on_device(b)) return rc;
+        b.ms_workers = ms_since(b.t_begin);
+        if (int rc = defilter_batched(b)) return rc;
+        decode_remaining(b);
+        return report(b);
     } catch (...) {
         return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "png_decode_batch_device: out of host memory");
     }

@@ -10,12 +10,16 @@ segments of small batches, the work queue, its rolling form, and for the expand 
 kernel, " seg=N" where images are cut into N row segments, and " + " the expand kernel where the rows go through the scratch."""
 import collections
 import functools
+import os
 import re
+import zlib
 
 import numpy as np
+import pytest
 
 import gen
 import oracle_lib as O
+from png_host_corpus import idat_stream, with_idat
 
 # (img_n, depth, color): the same fifteen as tests/test_png_gpu.py (test_png_batch_gpu.py asserts it)
 FORMATS = [(1, 1, 0), (1, 2, 0), (1, 4, 0), (1, 8, 0), (1, 16, 0), (2, 8, 4), (2, 16, 4), (3, 8, 2), (3, 16, 2), (4, 8, 6), (4, 16, 6),
@@ -377,3 +381,66 @@ def table_variant(fmt, form, out_addr=0, x=None, y=TABLE_HEIGHT, count=5):
     offs, _ = table_offsets([1] * (count + 1), form)
     return variant(w if x is None else x, y, ch, req, depth, count, out_addr, 0, offs=True,
                    offs_dword_aligned=out_addr % 4 == 0 and all(o % 4 == 0 for o in offs), offs_line_aligned=out_addr % 128 == 0 and all(o % 128 == 0 for o in offs))
+
+
+# ------------------------------------------------------------------------------------------------ the file-level batch call
+@pytest.fixture(params=["host", "device", "device, pitched staging", "device, tight staging"])
+def inflate_mode(request):
+    """where the IDAT streams of the PNG batch call are inflated: zlib on the host threads, or k_inflate on the GPU (inflate.hip: batches of more
+    files than host threads choose it themselves, GAMUT_HIP_PNG_INFLATE forces either) -- and, on the GPU, how the streams' slices go up: every
+    stream `pitch` bytes apart and one hipMemcpy2DAsync per slice round, or a tight image and a copy per (stream, slice) (the call picks by how
+    unequal the streams are; GAMUT_HIP_PNG_PITCHED forces either)"""
+    keys = ("GAMUT_HIP_PNG_INFLATE", "GAMUT_HIP_PNG_PITCHED", "GAMUT_HIP_PNG_SLICE_KB")
+    old = [os.environ.get(k) for k in keys]
+    os.environ["GAMUT_HIP_PNG_INFLATE"] = request.param.split(",")[0]
+    if "staging" in request.param:                               # 64 KiB slices: the larger files of the tests take several rounds
+        os.environ["GAMUT_HIP_PNG_PITCHED"] = "1" if "pitched" in request.param else "0"
+        os.environ["GAMUT_HIP_PNG_SLICE_KB"] = "64"
+    yield request.param.split(",")[0]
+    for k, v in zip(keys, old):
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+
+
+# what the batch call says of each kind of broken file (gamut_hip_last_error() behind "image N: "), written down from a run of the commit before the call was
+# split into stages
+FAILURE_TEXT = {"bad signature": "png: bad signature", "no IDAT": "png: no IDAT", "bad zlib header": "png: bad zlib header", "flipped bit": "png: corrupt zlib stream",
+                "cut short": "png: corrupt zlib stream", "filter 5, batched": "png: invalid filter", "filter 5, Adam7": "png: invalid filter", "no PLTE": "png: no PLTE"}
+
+
+@functools.lru_cache(maxsize=None)
+def failure_batch():
+    """[(kind or None, file)]: twelve files of 5x3 and 8x8, every kind of failure the file-level batch call tells apart, good files first, last and in between.
+    Three good 8x8 RGB8 files and the one with filter byte 5 share a geometry: one batched de-filter launch."""
+    rng = np.random.default_rng(404)
+
+    def rgb(w, h, **kw):
+        return gen.write_png(rng.integers(0, 256, (h, w * 3)), w, h, 2, 8, **kw)
+
+    def refiltered(data, row_bytes, row):                       # the file with filter byte 5 in front of a row of its (first) image
+        raw = bytearray(zlib.decompress(idat_stream(data)))
+        raw[row * (row_bytes + 1)] = 5
+        return with_idat(data, [zlib.compress(bytes(raw), 6)])
+
+    good = rgb(8, 8, filters=0)
+    z = idat_stream(good)
+    # one flipped bit that no decoder can take: a stored block's LEN no longer matches its NLEN, a coded block's BTYPE becomes 11
+    btype = (z[2] >> 1) & 3
+    flipped = z[:3] + bytes([z[3] ^ 1]) + z[4:] if btype == 0 else z[:2] + bytes([z[2] ^ (4 if btype == 1 else 2)]) + z[3:]
+    bad_header = bytearray(z[:2]); bad_header[1] = 0x79
+    files = [(None, rgb(5, 3)),
+             ("bad signature", b"\x88" + good[1:]),
+             (None, gen.write_png(rng.integers(0, 256, (8, 8 * 4)), 8, 8, 6, 8)),
+             ("no IDAT", with_idat(good, [])),
+             ("bad zlib header", with_idat(good, [bytes(bad_header[:1]), bytes(bad_header[1:])] + [z[i:i + 1] for i in range(2, len(z))])),
+             (None, rgb(8, 8)),
+             ("flipped bit", with_idat(good, [flipped])),
+             ("cut short", with_idat(good, [z[:len(z) // 2]])),
+             ("filter 5, batched", refiltered(good, 8 * 3, 4)),
+             ("filter 5, Adam7", refiltered(rgb(8, 8, interlace=1, filters=0), 1 * 3, 0)),
+             ("no PLTE", gen.write_png(rng.integers(0, 16, (3, 5)), 5, 3, 3, 4)),
+             (None, rgb(8, 8))]
+    assert len(files) == 12 and {k for k, _ in files if k} == set(FAILURE_TEXT)
+    return files

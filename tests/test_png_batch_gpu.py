@@ -14,6 +14,7 @@ import pytest
 import gen
 import oracle_lib as O
 import png_batch_cases as B
+from png_batch_cases import inflate_mode  # noqa: F401 -- the fixture, shared with test_png_gpu.py
 
 pytestmark = pytest.mark.gpu
 SENTINEL = 0x5A5A5A5A                                 # the words behind the status array
@@ -203,6 +204,61 @@ def test_offset_tables_on_and_off_the_lines(hip, inflate):
                 j = int(np.flatnonzero(got != exp)[0])
                 failures.append(f"{where}: allocation byte {j - G} (files start at {offs.tolist()}): got {got[j:j + 8].tolist()} want {exp[j:j + 8].tolist()}")
     assert not failures, f"{len(failures)} differences:\n" + "\n".join(failures[:8])
+
+
+def _decode_files(hip, files, req, offs, span):
+    """gamut_hip_png_decode_batch_device on three host threads into an allocation of 0xA5 -> (return code, status per file, message, the allocation)"""
+    from gamut_amd import _capi
+    n = len(files)
+    bufs = [np.frombuffer(f, np.uint8) for f in files]
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs]); lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    d_out = _DeviceBuffer(hip, span)
+    try:
+        d_out.upload(np.full(span, 0xA5, np.uint8))
+        info = (_capi.PngInfo * n)(); st = (C.c_int * n)()
+        rc = hip.gamut_hip_png_decode_batch_device(ptrs, lens, n, req, 8, offs.ctypes.data_as(C.POINTER(C.c_int64)), d_out.ptr + B.GUARD, info, st, 3, None)
+        msg = hip.gamut_hip_last_error().decode()
+        _capi.check(hip.gamut_hip_stream_synchronize(None))
+        return rc, list(st), msg, d_out.download(span)
+    finally:
+        d_out.free()
+
+
+@pytest.mark.parametrize("req", [4, 0])
+def test_every_failure_kind_in_one_batch(hip, inflate_mode, req):
+    """twelve files of 5x3 and 8x8 in one call, eight of them broken, each in its own way (png_batch_cases.failure_batch), good ones first, last and in between: the status
+    is non-zero exactly where the oracle's stbi_load refuses the file, every other file == the oracle, the allocation is 0xA5 outside the good files (the one
+    exception, as everywhere in this file: the own bytes of the two files with a bad filter byte, which the de-filter meets when the file's pixels are already on their
+    way -- so it was before the call was split into stages), the return code and the message are the first broken file's.
+    Then each broken file behind one good one: its own message."""
+    from gamut_amd import _capi
+    G = B.GUARD
+    batch = B.failure_batch()
+    files = [f for _, f in batch]
+    want = [O.stbi_load(f, req, False) for f in files]
+    assert [w is None for w in want] == [k is not None for k, _ in batch]
+    px = [None if w is None else np.ascontiguousarray(w[0]).reshape(-1) for w in want]
+    offs, span = B.table_offsets([8 * 8 * 4 if p is None else p.size for p in px], "odd")
+    span += 2 * G
+    rc, st, msg, got = _decode_files(hip, files, req, offs, span)
+    exp, mask = np.full(span, 0xA5, np.uint8), np.ones(span, bool)
+    for i, (kind, _) in enumerate(batch):
+        at = G + int(offs[i])
+        if px[i] is not None:
+            exp[at:at + px[i].size] = px[i]
+        elif kind.startswith("filter 5"):                    # (the rows in front of the bad byte are there -- the batched launch -- or what png_run made of them)
+            mask[at:at + 8 * 8 * (req or 3)] = False
+    where = f"inflate on the {inflate_mode}, req_comp {req}"
+    assert [s != 0 for s in st] == [p is None for p in px], (where, st)
+    assert np.array_equal(got[mask], exp[mask]), (where, (np.flatnonzero((got != exp) & mask)[:8] - G).tolist(), offs.tolist())
+    first = next(i for i, p in enumerate(px) if p is None)
+    assert rc == st[first] == _capi.ERR_DECODE and msg == f"image {first}: {B.FAILURE_TEXT[batch[first][0]]}", (where, rc, st, msg)
+    for kind, f in batch:
+        if kind is None:
+            continue
+        o2, s2 = B.table_offsets([px[0].size, 8 * 8 * 4], "odd")
+        rc, st, msg, _ = _decode_files(hip, [files[0], f], req, o2, s2 + 2 * G)
+        assert (rc, st, msg) == (_capi.ERR_DECODE, [0, _capi.ERR_DECODE], f"image 1: {B.FAILURE_TEXT[kind]}"), (where, kind, rc, st, msg)
 
 
 @pytest.mark.parametrize("img_n,depth,x,y", [(1, 1, 8, 2), (2, 16, 2, 2)], ids=["grey1-8x2", "greyalpha16-2x2"])

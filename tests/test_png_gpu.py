@@ -9,6 +9,7 @@ import pytest
 import gen
 import oracle_lib as O
 from gamut_amd import _capi
+from png_batch_cases import inflate_mode  # noqa: F401 -- the fixture, shared with test_png_batch_gpu.py
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -314,26 +315,6 @@ def test_extreme_geometry(hip, launch_mode, img_n, out_n, x, y):
     exp = O.png_create_image_raw(raw, img_n, out_n, x, y, 8, color)
     got = gpu_defilter(hip, raw, x, y, img_n, out_n, 8, color)[0]
     assert np.array_equal(got, exp)
-
-
-@pytest.fixture(params=["host", "device", "device, pitched staging", "device, tight staging"])
-def inflate_mode(request):
-    """where the IDAT streams of the PNG batch call are inflated: zlib on the host threads, or k_inflate on the GPU (inflate.hip: batches of more
-    files than host threads choose it themselves, GAMUT_HIP_PNG_INFLATE forces either) -- and, on the GPU, how the streams' slices go up: every
-    stream `pitch` bytes apart and one hipMemcpy2DAsync per slice round, or a tight image and a copy per (stream, slice) (the call picks by how
-    unequal the streams are; GAMUT_HIP_PNG_PITCHED forces either)"""
-    keys = ("GAMUT_HIP_PNG_INFLATE", "GAMUT_HIP_PNG_PITCHED", "GAMUT_HIP_PNG_SLICE_KB")
-    old = [os.environ.get(k) for k in keys]
-    os.environ["GAMUT_HIP_PNG_INFLATE"] = request.param.split(",")[0]
-    if "staging" in request.param:                               # 64 KiB slices: the larger files of the tests take several rounds
-        os.environ["GAMUT_HIP_PNG_PITCHED"] = "1" if "pitched" in request.param else "0"
-        os.environ["GAMUT_HIP_PNG_SLICE_KB"] = "64"
-    yield request.param.split(",")[0]
-    for k, v in zip(keys, old):
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
 
 
 def test_png_file_batch_feeder(hip, inflate_mode):
