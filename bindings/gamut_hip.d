@@ -206,6 +206,21 @@ extern(C)
     float gamut_hip_tga_last_encode_kernel_ms();
     float gamut_hip_tga_last_encode_stage_ms(int stage);
 
+    // QOIX, 8-bit rgb / rgba: qoix_lz4_decode (plugins/qoix.d:350-473), LZ4_decompress_fast (codecs/lz4.d:760-978) and qoix_decode
+    // (codecs/qoi2avg.d:624-897) on the GPU.  read_header: info.detected is detectQOIX's verdict, the return value the load's
+    // (GAMUT_HIP_ERR_UNSUPPORTED for the grey and 10-bit codecs, which are not built yet).  Deviations, each GAMUT_HIP_ERR_DECODE: an LZ4
+    // read past the file's end; LZ4 offset 0 or a match from before the first output byte; an executed END opcode; an op byte read at
+    // index >= size.
+    struct gamut_hip_qoix_info { int width, height, version_, channels, bitdepth, colorspace, compression; float pixel_aspect_ratio, resolution_y;
+                                 int orig, pixel_type, detected; }
+    int   gamut_hip_qoix_read_header(const(ubyte)* data, size_t len, gamut_hip_qoix_info* info);
+    int   gamut_hip_qoix_decode_batch_device(const(ubyte*)* data, const(size_t)* len, int count, int channels, const(long)* out_offset,
+                                             ubyte* out_, gamut_hip_qoix_info* info, int* status_host, void* stream);
+    void* gamut_hip_qoix_lz4_decode(const(void)* data, int size, gamut_hip_qoix_info* info, int flags, int* decoded_type);
+    int   gamut_hip_qoix_row_capacity();
+    float gamut_hip_qoix_last_decode_kernel_ms();
+    float gamut_hip_qoix_last_decode_stage_ms(int stage);
+
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }
     int gamut_hip_identify_format(const(ubyte)* data, size_t len);
@@ -239,6 +254,9 @@ extern(C)
     static assert(gamut_hip_image_info.sizeof == 20 && gamut_hip_image_info.format.offsetof == 0 && gamut_hip_image_info.width.offsetof == 4 && gamut_hip_image_info.height.offsetof == 8 && gamut_hip_image_info.channels_in_file.offsetof == 12 && gamut_hip_image_info.channels.offsetof == 16);
     // (the TGA struct's numbers are the ones tests/c/tga_abi_layout.c prints; tests/test_tga_cpu.py compares them every run)
     static assert(56 == gamut_hip_tga_info.sizeof && 0 == gamut_hip_tga_info.width.offsetof && 4 == gamut_hip_tga_info.height.offsetof && 8 == gamut_hip_tga_info.bpp.offsetof && 12 == gamut_hip_tga_info.image_type.offsetof && 16 == gamut_hip_tga_info.rle.offsetof && 20 == gamut_hip_tga_info.indexed.offsetof && 24 == gamut_hip_tga_info.rgb16.offsetof && 28 == gamut_hip_tga_info.channels_in_file.offsetof && 32 == gamut_hip_tga_info.bottom_up.offsetof && 36 == gamut_hip_tga_info.palette_start.offsetof && 40 == gamut_hip_tga_info.palette_len.offsetof && 44 == gamut_hip_tga_info.cmap_size.offsetof && 48 == gamut_hip_tga_info.data_offset.offsetof && 52 == gamut_hip_tga_info.detected.offsetof);
+    // (the QOIX struct's numbers are the ones tests/c/qoix_abi_layout.c prints; tests/test_qoix_cpu.py compares them every run.  `version` is a
+    //  D keyword: the field is version_ here)
+    static assert(48 == gamut_hip_qoix_info.sizeof && 0 == gamut_hip_qoix_info.width.offsetof && 4 == gamut_hip_qoix_info.height.offsetof && 8 == gamut_hip_qoix_info.version_.offsetof && 12 == gamut_hip_qoix_info.channels.offsetof && 16 == gamut_hip_qoix_info.bitdepth.offsetof && 20 == gamut_hip_qoix_info.colorspace.offsetof && 24 == gamut_hip_qoix_info.compression.offsetof && 28 == gamut_hip_qoix_info.pixel_aspect_ratio.offsetof && 32 == gamut_hip_qoix_info.resolution_y.offsetof && 36 == gamut_hip_qoix_info.orig.offsetof && 40 == gamut_hip_qoix_info.pixel_type.offsetof && 44 == gamut_hip_qoix_info.detected.offsetof);
     // (the BMP struct's numbers are the ones tests/c/bmp_abi_layout.c prints; tests/test_bmp_cpu.py compares them every run)
     static assert(64 == gamut_hip_bmp_info.sizeof && 0 == gamut_hip_bmp_info.width.offsetof && 4 == gamut_hip_bmp_info.height.offsetof && 8 == gamut_hip_bmp_info.bpp.offsetof && 12 == gamut_hip_bmp_info.header_size.offsetof && 16 == gamut_hip_bmp_info.compression.offsetof && 20 == gamut_hip_bmp_info.channels_in_file.offsetof && 24 == gamut_hip_bmp_info.top_down.offsetof && 28 == gamut_hip_bmp_info.pixel_offset.offsetof && 32 == gamut_hip_bmp_info.palette_size.offsetof && 36 == gamut_hip_bmp_info.mask_r.offsetof && 40 == gamut_hip_bmp_info.mask_g.offsetof && 44 == gamut_hip_bmp_info.mask_b.offsetof && 48 == gamut_hip_bmp_info.mask_a.offsetof && 52 == gamut_hip_bmp_info.pixels_per_meter_x.offsetof && 56 == gamut_hip_bmp_info.pixels_per_meter_y.offsetof && 60 == gamut_hip_bmp_info.pixel_aspect_ratio.offsetof);
     // (the GIF struct's numbers are the ones tests/c/gif_abi_layout.c prints; tests/test_gif_cpu.py compares them every run)

@@ -57,6 +57,12 @@ class TgaInfo(C.Structure):                                    # gamut_hip_tga_i
                                          "palette_start", "palette_len", "cmap_size", "data_offset", "detected")]
 
 
+class QoixInfo(C.Structure):                                   # gamut_hip_qoix_info
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("version", C.c_int32), ("channels", C.c_int32), ("bitdepth", C.c_int32),
+                ("colorspace", C.c_int32), ("compression", C.c_int32), ("pixel_aspect_ratio", C.c_float), ("resolution_y", C.c_float),
+                ("orig", C.c_int32), ("pixel_type", C.c_int32), ("detected", C.c_int32)]
+
+
 class ImageInfo(C.Structure):                                  # gamut_hip_image_info
     _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels_in_file", C.c_int32), ("channels", C.c_int32)]
 
@@ -142,6 +148,12 @@ SIGNATURES = {
     "gamut_hip_tga_encode_window": (_i, []),
     "gamut_hip_tga_last_encode_kernel_ms": (_f, []),
     "gamut_hip_tga_last_encode_stage_ms": (_f, [_i]),
+    "gamut_hip_qoix_read_header": (_i, [_vp, _sz, C.POINTER(QoixInfo)]),
+    "gamut_hip_qoix_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _i, C.POINTER(_i64), _vp, C.POINTER(QoixInfo), _pi, _vp]),
+    "gamut_hip_qoix_lz4_decode": (_vp, [_vp, _i, C.POINTER(QoixInfo), _i, _pi]),
+    "gamut_hip_qoix_row_capacity": (_i, []),
+    "gamut_hip_qoix_last_decode_kernel_ms": (_f, []),
+    "gamut_hip_qoix_last_decode_stage_ms": (_f, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

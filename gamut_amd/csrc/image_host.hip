@@ -454,6 +454,29 @@ struct gamut_image {
         _layoutConstraints = 0;
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);
     }
+    void loadQOIX(const uint8_t* bytes, size_t len, int flags)                              // plugins/qoix.d:64-146
+    {
+        const int requested = computeRequestedImageComponents(flags);                       // :92-99: only its verdict is used
+        if (requested == 0) { error(kStrInvalidFlags); return; }
+        gamut_hip_qoix_info hd, info;
+        // qoix_lz4_decode :112: the flags are only validated, decodedType = streamType; a sub-codec that is not built yet fails the same way
+        if (!validLoadFlags(flags) || gamut_hip_qoix_read_header(bytes, len, &hd) != GAMUT_HIP_OK) { error(kStrImageDecodingFailed); return; }
+        const int comps = hd.channels;
+        const size_t nbytes = (size_t)hd.width * hd.height * comps;
+        // the decode is the GPU's either way: a device image keeps the allocation (its rows are tight), a host image gets the pixels copied back
+        uint8_t* dev = dmalloc(nbytes);
+        const int64_t zero = 0; int st = 0;
+        if (!dev || gamut_hip_qoix_decode_batch_device(&bytes, &len, 1, 0, &zero, dev, &info, &st, nullptr) != GAMUT_HIP_OK) {
+            if (dev) (void)hipFree(dev);
+            error(kStrImageDecodingFailed); return;
+        }
+        uint8_t* decoded = residentOrHostCopy(dev, nbytes);
+        if (!decoded) { error(kStrImageDecodingFailed); return; }
+        if (!imageIsValidSize(1, hd.width, hd.height)) { error(kStrImageTooLarge); release(decoded); return; }     // :122-127
+        adopt(decoded, hd.width, hd.height, hd.pixel_type, comps, hd.pixel_aspect_ratio, hd.resolution_y);          // :129-142, pitch = width * channels
+        _layoutConstraints = 0;                                                             // :135
+        convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);                           // :145
+    }
     void loadBMP(const uint8_t* bytes, size_t len, int flags)                               // plugins/bmp.d:85-163
     {
         int requested = computeRequestedImageComponents(flags);
@@ -541,6 +564,7 @@ static int identify(const uint8_t* b, size_t len)
     if (b && len >= 2 && b[0] == 0xFF && b[1] == 0xD8) return GAMUT_FORMAT_JPEG;            // detectJPEG plugins/jpeg.d:106-110
     if (b && len >= 8 && !memcmp(b, png, 8)) return GAMUT_FORMAT_PNG;                       // detectPNG plugins/png.d:165-169
     if (b && len >= 4 && !memcmp(b, "qoif", 4)) return GAMUT_FORMAT_QOI;                    // detectQOI plugins/qoi.d:144-148
+    if (b && len >= 4 && !memcmp(b, "qoix", 4)) return GAMUT_FORMAT_QOIX;                   // detectQOIX plugins/qoix.d:149-153 ('o' cannot be a TGA colour-map type)
     if (b && len >= 6 && (!memcmp(b, "GIF87a", 6) || !memcmp(b, "GIF89a", 6))) return GAMUT_FORMAT_GIF;   // detectGIF plugins/gif.d:42-53
     if (gamut_hip_identify_format(b, len) == GAMUT_HIP_FORMAT_BMP) return GAMUT_FORMAT_BMP;  // detectBMP plugins/bmp.d:45-82
     if (gamut_hip_identify_format(b, len) == GAMUT_HIP_FORMAT_TGA) return GAMUT_FORMAT_TGA;  // detectTGA plugins/tga.d:97-126, last (image.d:1056)
@@ -592,6 +616,7 @@ int gamut_image_load_from_memory(gamut_image* img, const uint8_t* bytes, size_t 
     case GAMUT_FORMAT_JPEG: img->loadJPEG(bytes, len, flags); break;
     case GAMUT_FORMAT_PNG:  img->loadPNG(bytes, len, flags); break;
     case GAMUT_FORMAT_QOI:  img->loadQOI(bytes, len, flags); break;
+    case GAMUT_FORMAT_QOIX: img->loadQOIX(bytes, len, flags); break;
     case GAMUT_FORMAT_BMP:  img->loadBMP(bytes, len, flags); break;
     case GAMUT_FORMAT_GIF:  img->loadGIF(bytes, len, flags); break;
     case GAMUT_FORMAT_TGA:  img->loadTGA(bytes, len, flags); break;

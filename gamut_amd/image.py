@@ -54,6 +54,7 @@ TO_GREYSCALE, TO_RGB, TO_ADD_ALPHA, TO_DROP_ALPHA, TO_PREMUL, TO_NO_PREMUL, TO_8
 LOAD_GREYSCALE, LOAD_ALPHA, LOAD_NO_ALPHA, LOAD_RGB = 0x10000, 0x20000, 0x40000, 0x80000
 LOAD_8BIT, LOAD_16BIT, LOAD_FP32, LOAD_PREMUL, LOAD_NO_PREMUL = 0x100000, 0x200000, 0x400000, 0x1000000, 0x2000000
 FORMAT_UNKNOWN, FORMAT_JPEG, FORMAT_PNG, FORMAT_QOI = -1, 0, 1, 2
+FORMAT_QOIX = 3                                                # ImageFormat.QOIX: read (loadFromMemory), 8-bit rgb / rgba files; not written yet
 FORMAT_GIF = 6                                                 # ImageFormat.GIF: every frame a layer, read and written (rgba8)
 FORMAT_TGA = 5                                                 # ImageFormat.TGA: read (loadFromMemory) and written (save_tga_to_memory); save_to_memory(5) returns None
 FORMAT_BMP = 7                                                 # ImageFormat.BMP (types.d:14-28)

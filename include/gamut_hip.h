@@ -602,6 +602,60 @@ int     gamut_hip_tga_encode_window(void);
 float   gamut_hip_tga_last_encode_kernel_ms(void);
 float   gamut_hip_tga_last_encode_stage_ms(int stage);
 
+/* ---- QOIX, 8-bit rgb / rgba (qoix_lz4_decode, plugins/qoix.d:350-473; LZ4_decompress_fast, codecs/lz4.d:760-978; qoix_decode,
+ * codecs/qoi2avg.d:624-897) ------------------------------------------------------------------------------------------------------
+ * Decode: every pixel what the reference gives, bit for bit, for files that hold 8-bit rgb or rgba (what saveQOIX writes for rgb8,
+ * rgba8 and rgbap8), stored or LZ4-compressed.  Kept from the reference: the load flags are only validated and the decoder produces
+ * the file's own channel count; the last four bytes are never decoded as opcodes and never checked; a stream that ends early repeats
+ * the last pixel and surplus ops are ignored; runs cross row ends and are cut at the image's end; a 3-channel file may carry ADIFF
+ * and RGBA ops, whose alpha shows when 4 channels are asked for; whatever follows the LZ4 block's final literal run is ignored.
+ * The grey codecs (8-bit with 1 or 2 channels) and the 10-bit codecs are not built yet: GAMUT_HIP_ERR_UNSUPPORTED.
+ * Deliberate deviations, each where the reference touches memory it does not own, each GAMUT_HIP_ERR_DECODE:
+ *   1. LZ4: any read at or past the end of the file refuses the file (the reference has no input bound);
+ *   2. LZ4: offset 0, or a match that starts before the first output byte, refuses the file (the reference reads up to 64 KiB in
+ *      front of its buffer);
+ *   3. QOI2AVG: an END opcode that is executed refuses the file (the reference leaves the rest of the row as whatever its scanline
+ *      buffer held, uninitialised memory in rows 0 and 1); no valid file executes END;
+ *   4. QOI2AVG: an op byte read at index >= size refuses the file (an ADIFF chain running through the last four bytes).
+ * Also refused: a length above INT_MAX (loadQOIX keeps it in an int), and an `orig` above 255 * (length - 29), which no LZ4 block
+ * of that length can produce (it could only end in deviation 1).
+ * (Declared typedef-first: the layout of this struct is pinned by tests/c/qoix_abi_layout.c and tests/test_qoix_cpu.py.) */
+typedef struct gamut_hip_qoix_info gamut_hip_qoix_info;
+struct gamut_hip_qoix_info {
+    int32_t width, height;          /* the header's big-endian u32 fields */
+    int32_t version, channels, bitdepth, colorspace, compression;      /* bytes 12..16 */
+    float   pixel_aspect_ratio;     /* bytes 17..20, bit for bit */
+    float   resolution_y;           /* bytes 21..24, bit for bit: vertical DPI */
+    int32_t orig;                   /* compression 1: the big-endian int at bytes 25..28; else 0 */
+    int32_t pixel_type;             /* identifyTypeFromStream's GAMUT_PIXEL_* (rgbap8 for colorspace 2 with 4 channels), -1 when it refuses */
+    int32_t detected;               /* 1: the file starts with "qoix" (detectQOIX), whatever the load verdict is */
+};
+/* the header alone (host, no GPU needed).  info->detected is detectQOIX's verdict, the return value the load's on everything that
+ * is decidable without the body: GAMUT_HIP_OK, GAMUT_HIP_ERR_UNSUPPORTED for a header the container accepts but whose codec is not
+ * built yet (bitdepth 10, or 8-bit with 1 or 2 channels), GAMUT_HIP_ERR_DECODE for a refusal.  Fields are filled as far as the
+ * header was read. */
+int gamut_hip_qoix_read_header(const uint8_t* data, size_t len, gamut_hip_qoix_info* info);
+/* `count` QOIX files in host memory -> tight rows of width * channels bytes at out + out_offset[i] (device, any alignment).
+ * channels 0: the file's own count; 3 / 4 as in qoix_decode (alpha dropped / kept, 255 unless ADIFF or RGBA ops set it); anything
+ * else is GAMUT_HIP_ERR_INVALID_ARG.  Two launches whatever the batch holds: one over the LZ4 files (a wave each; skipped when there
+ * are none), one over all op streams (a wave each).  info[i] / status_host[i] (either may be NULL) per file; a failing file gets its
+ * status and does not disturb the others; returns the status of the lowest-numbered failing file, whose number the tail of
+ * last_error names ("image %d:").  A file refused on the host writes nothing; one refused on the device (the verdict is the
+ * kernels' status word, not a host pre-walk) may leave anything inside its own width * height * channels bytes.  Nothing outside
+ * those bytes is written.  The files go up through pinned staging; returns when the pixels are in place. */
+int gamut_hip_qoix_decode_batch_device(const uint8_t* const* data, const size_t* len, int count, int channels,
+                                       const int64_t* out_offset, uint8_t* out, gamut_hip_qoix_info* info, int* status_host, void* stream);
+/* host drop-in with qoix_lz4_decode's argument list: the pixels (the file's own channel count, tight rows) in a malloc'd buffer and
+ * *decoded_type = the stream's GAMUT_PIXEL_*, or NULL (flags that validLoadFlags refuses, a refused file, no device) */
+void* gamut_hip_qoix_lz4_decode(const void* data, int size, gamut_hip_qoix_info* info, int flags, int* decoded_type);
+/* the op-stream kernel keeps rows of up to this many pixels in LDS; a wider row lives in a global scratch row */
+int   gamut_hip_qoix_row_capacity(void);
+/* measurements: with GAMUT_HIP_QOIX_TIMING=1 the decode call brackets its kernels (not the upload) with events; the GPU milliseconds
+ * of the calling thread's last decode call -- both kernels, or one (stage 0: LZ4, 1: op streams); -1 when timing is off, nothing was
+ * decoded or `stage` is out of range */
+float gamut_hip_qoix_last_decode_kernel_ms(void);
+float gamut_hip_qoix_last_decode_stage_ms(int stage);
+
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
  * procedures, a signature test each: plugins/jpeg.d:106-110, png.d:165-169, qoi.d:143-147) picks g_plugins[fif].loadProc
