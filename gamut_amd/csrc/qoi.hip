@@ -141,21 +141,22 @@ template <int CTRL, int ROWMASK> __device__ __forceinline__ void qoi_scan_step(Q
 // 24 + ~20 vector instructions instead of 83 + 12.  Alpha only changes at RGBA and INDEX ops: groups without either (six in ten of
 // a photograph's) skip it, groups with INDEX ops only mark the lanes from the first one on, RGBA ops take a scan of their own.
 // The result is the same (M, V, U) the composition gives, bit for bit (U a subset of M, V's alpha 0 unless an RGBA op set it).
-#define GAMUT_QOI_SCAN4(CTRL) asm volatile("v_add_u32_dpp %0, %0, %0 " CTRL "\n\tv_add_u32_dpp %1, %1, %1 " CTRL "\n\tv_add_u32_dpp %2, %2, %2 " CTRL "\n\tv_max_u32_dpp %3, %3, %3 " CTRL \
-                                           : "+v"(pe), "+v"(po), "+v"(n), "+v"(jm))
+// (WAIT: the first block reads registers the instruction in front of it may have written -- two wait states, as in qoi_add_scan_step -- and
+// the wait stands INSIDE its asm statement: a statement of its own is not tied to the block, and the compiler may put anything between the two.)
+#define GAMUT_QOI_SCAN4(WAIT, CTRL) asm volatile(WAIT "v_add_u32_dpp %0, %0, %0 " CTRL "\n\tv_add_u32_dpp %1, %1, %1 " CTRL "\n\tv_add_u32_dpp %2, %2, %2 " CTRL "\n\tv_max_u32_dpp %3, %3, %3 " CTRL \
+                                                 : "+v"(pe), "+v"(po), "+v"(n), "+v"(jm))
 template <int CTRL, int ROWMASK> __device__ __forceinline__ void qoi_max_scan_step(uint32_t& v) { const uint32_t p = qoi_dpp<CTRL, ROWMASK>(v, 0u); v = p > v ? p : v; }
 // lane: 0..63; dE = R | B << 16 and dO = G: the deltas of a DIFF / LUMA op (0 for every other op); m_stream = all ones for an RGB / RGBA
 // op (bytes 1..4 of the op are v_abs); n: in = the op's run length, out = the inclusive prefix sum
 __device__ __forceinline__ QoiFn qoi_group_scan(int lane, uint32_t dE, uint32_t dO, uint32_t m_stream, bool is_index, bool is_rgba, uint32_t v_abs, uint32_t& n)
 {
     uint32_t pe = dE, po = dO, jm = (m_stream != 0u || is_index) ? (uint32_t)lane + 1u : 0u;
-    asm volatile("s_nop 1");
-    GAMUT_QOI_SCAN4("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-    GAMUT_QOI_SCAN4("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-    GAMUT_QOI_SCAN4("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-    GAMUT_QOI_SCAN4("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1");
-    GAMUT_QOI_SCAN4("row_bcast:15 row_mask:0xa bank_mask:0xf");
-    GAMUT_QOI_SCAN4("row_bcast:31 row_mask:0xc bank_mask:0xf");
+    GAMUT_QOI_SCAN4("s_nop 1\n\t", "row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    GAMUT_QOI_SCAN4("", "row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    GAMUT_QOI_SCAN4("", "row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    GAMUT_QOI_SCAN4("", "row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1");
+    GAMUT_QOI_SCAN4("", "row_bcast:15 row_mask:0xa bank_mask:0xf");
+    GAMUT_QOI_SCAN4("", "row_bcast:31 row_mask:0xc bank_mask:0xf");
     const uint32_t qE = (v_abs & m_stream & 0x00FF00FFu) - pe, qO = ((v_abs >> 8) & m_stream & 0xFFu) - po;
     const int addr = (int)(jm << 2) - 4;
     const bool none = jm == 0u;

@@ -2,8 +2,9 @@
 header and a list of ops, the constructed cases, and the arbitrary streams no encoder writes.  The geometry the cases are laid out
 against -- window, bytes per lane of the one-wave kernel, the pixel-buffer threshold, the batch thresholds -- is read from the kernels'
 source (the library has no query for it yet), never written down here.  tests/test_qoi_cases_cpu.py checks, without a GPU, that every
-property a case is named for is really in its bytes, and the oracle against a second decoder on all of them.  The arbitrary streams
-go through the kernels in tests/test_qoi_gpu.py; the constructed ones have no GPU test yet."""
+property a case is named for is really in its bytes, and the oracle against a second decoder on all of them.  On the GPU every case,
+constructed and arbitrary, goes through all three decode kernels at output channels 0, 3 and 4 in tests/test_qoi_batch_gpu.py (laid
+out by tests/qoi_batch.py); the arbitrary streams also run in tests/test_qoi_gpu.py."""
 import collections
 import functools
 import os

@@ -1,13 +1,21 @@
 """The case list of tests/qoi_cases.py, checked without a GPU: an op walker that lays every stream out as the decode kernels see it (windows of
 param(0) chunk bytes, groups of 64 ops per window, lanes of param(1) bytes) finds each property a case is named for in its bytes, and a second
-decoder, written from the reference's text, agrees with the oracle on streams no encoder writes."""
+decoder, written from the reference's text, agrees with the oracle on streams no encoder writes.  The second half checks the launch layouts
+of tests/qoi_batch.py that tests/test_qoi_batch_gpu.py runs the cases in: where the streams and their pixels lie, and which kernel a launch gets."""
 import collections
+import ctypes as C
+import functools
+import gc
+import os
+import re
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+import qoi_batch as B
 import qoi_cases as Q
+from gamut_amd import _capi
 
 Op = collections.namedtuple("Op", "n off len kind win idx group lane first_px npx run px slot src executed")
 Group = collections.namedtuple("Group", "win group ops before waiting total straight")
@@ -300,3 +308,124 @@ def test_the_walker_agrees_with_the_oracle():
 def test_the_case_list():
     assert len(Q.CONSTRUCTED) == 3 * 8 * 2 + 9 + 8 + 7 + 9 + 1 and len(Q.ARBITRARY) == 40 and len({c.data for c in Q.CASES}) == len(Q.CASES)
     assert not Q.expected(Q.CASES[0].name, 4).flags.writeable
+
+
+# ---- the launch layouts of tests/qoi_batch.py, as tests/test_qoi_batch_gpu.py uses them ------------------------------------------------------------
+
+def _resident_layouts():
+    """(label, layout, runs one wave per stream) of every resident launch of test_qoi_batch_gpu.py"""
+    out = [(f"{kernel}-{ch}", B.resident(kernel, ch), kernel == "one_wave") for kernel in ("one_wave", "phases") for ch in (0, 3, 4)]
+    out += [(f"threshold-{n}-{ch}", B.threshold(n, ch), n >= Q.WIDE_BELOW) for n in (Q.WIDE_BELOW - 1, Q.WIDE_BELOW) for ch in (4, 3)]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _layouts():
+    return _resident_layouts()
+
+
+def test_the_layouts_run_the_kernel_they_are_named_for():
+    for label, L, one_wave in _layouts():
+        assert (L.n >= Q.WIDE_BELOW) == one_wave, label
+    assert B.resident("one_wave", 4).n == B.ONE_WAVE_COPIES * len(Q.CASES) == 854 and B.resident("pipeline", 4).n == len(Q.CASES) == 122
+    assert [L.n for label, L, _ in _layouts() if label.startswith("threshold")] == [Q.WIDE_BELOW - 1] * 2 + [Q.WIDE_BELOW] * 2
+    assert [s for s in B.threshold(Q.WIDE_BELOW - 1, 4).streams] == B.resident("one_wave", 4).streams[:Q.WIDE_BELOW - 1]     # the first streams of the same list
+    # from host memory: all cases are one launch, three times all cases are two, and neither reaches the one-wave kernel
+    assert B.host(1, 0).n == len(Q.CASES) <= Q.HOST_GROUP < B.host(3, 0).n == 3 * len(Q.CASES) <= 2 * Q.HOST_GROUP and Q.HOST_GROUP < Q.WIDE_BELOW
+    assert [c.name.rsplit("-", 3)[0] for c in B.drop_in_cases()[:3]] == ["straddle-window", "straddle-lane", "straddle-end"] and len(B.drop_in_cases()) == 8
+    assert all(c in Q.CONSTRUCTED for c in B.drop_in_cases()) and len({c.name for c in B.drop_in_cases()}) == 8
+
+
+def test_every_stream_lies_in_the_blob_with_its_slack():
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gamut_hip.h")).read()
+    assert [int(x) for x in re.findall(r"#define GAMUT_HIP_QOI_SLACK (\d+)", header)] == [B.SLACK]
+    assert B.DESC.itemsize == C.sizeof(_capi.QoiDesc) == 12 and [B.DESC.fields[f][1] for f in ("width", "height", "channels", "colorspace")] == [
+        getattr(_capi.QoiDesc, f).offset for f in ("width", "height", "channels", "colorspace")]
+    for label, L, _ in _layouts():
+        assert (L.begin.dtype, L.out_offset.dtype, L.size.dtype, L.blob.dtype) == (np.int64, np.int64, np.int32, np.uint8), label
+        assert L.begin[0] % 2 == 1 and L.blob.size == L.blob_len == int(L.begin[-1]) + int(L.size[-1]) + B.SLACK, label
+        for i, s in enumerate(L.streams):
+            assert L.blob[L.begin[i]:L.begin[i] + L.size[i]].tobytes() == s.case.data, (label, s.case.name)
+            assert (L.descs[i]["width"], L.descs[i]["height"], L.descs[i]["channels"]) == Q.header(s.case.data), (label, s.case.name)
+        ends = L.begin + L.size
+        assert (L.begin[1:] - ends[:-1] >= B.SLACK).all() and (ends + B.SLACK <= L.blob_len).all(), label
+        res = L.begin % 64
+        assert (res[1:] != res[:-1]).all() and set(res.tolist()) == set(range(64)), label
+        # what lies between the streams: every kind of fill, really there -- a stream's fill lies in front of it (the slack of the stream before),
+        # and the last stream's behind it as well
+        assert {s.fill for s in L.streams} == set(B.FILLS), label
+        for kind, byte in (("zeros", 0), ("0xFF", 0xFF), ("0xFE", 0xFE), ("0xFD", 0xFD)):
+            hit = [i for i in range(1, L.n) if L.streams[i].fill == kind]
+            assert hit, (label, kind)
+            assert all((L.blob[ends[i - 1]:L.begin[i]] == byte).all() and L.begin[i] - ends[i - 1] >= B.SLACK for i in hit), (label, kind)
+            if L.streams[-1].fill == kind:
+                assert (L.blob[ends[-1]:] == byte).all() and L.blob_len - ends[-1] == B.SLACK
+        i = [k for k in range(1, L.n) if L.streams[k].fill == "stream"][0]
+        gap = L.blob[ends[i - 1]:L.begin[i]].tobytes()
+        assert gap[:4] == b"qoif" and gap == (L.streams[i].case.data * (len(gap) // L.size[i] + 1))[:len(gap)]
+        i = [k for k in range(1, L.n) if L.streams[k].fill == "noise"][0]
+        assert len(set(L.blob[ends[i - 1]:L.begin[i]].tolist())) > 64
+    # a copy differs from the next one in what lies around it: with seven copies, every case meets every fill
+    L = B.resident("one_wave", 0)
+    assert all({s.fill for s in L.streams if s.case.name == c.name} == set(B.FILLS) for c in Q.CASES)
+
+
+def test_no_two_output_ranges_touch():
+    hosts = [(f"host-{k}-{ch}", B.host(k, ch), False) for k in (1, 3) for ch in (0, 3)]
+    for label, L, _ in _layouts() + hosts:
+        ends = L.out_offset + L.out_bytes
+        gaps = np.concatenate([L.out_offset[:1], L.out_offset[1:] - ends[:-1], [L.out_len - ends[-1]]])
+        assert gaps.min() >= 1 and gaps.max() <= 67 and L.poison.size == L.out_len and (L.poison == B.POISON).all(), label
+        assert [int(x) for x in L.out_bytes] == [Q.expected(s.case.name, L.channels).size for s in L.streams]
+        # three- and four-channel outputs each begin at every residue mod 16 (an output of `channels` 0 has its file's count)
+        assert set(L.out_channels.tolist()) == ({3, 4} if L.channels == 0 else {L.channels}), label
+        for ch in set(L.out_channels.tolist()):
+            assert set((L.out_offset[L.out_channels == ch] % 16).tolist()) == set(range(16)), (label, ch)
+        exp = L.expected_allocation()
+        assert not exp.flags.writeable and exp is L.expected_allocation()
+        inside = np.zeros(L.out_len, bool)
+        for i, s in enumerate(L.streams):
+            assert np.array_equal(exp[L.out_offset[i]:ends[i]], Q.expected(s.case.name, L.channels)), (label, s.case.name)
+            inside[L.out_offset[i]:ends[i]] = True
+        assert (exp[~inside] == B.POISON).all() and inside.sum() == L.out_bytes.sum()
+
+
+def test_a_wrong_byte_is_reported_by_the_name_of_its_case():
+    L = B.resident("one_wave", 0)
+    got = L.expected_allocation().copy()
+    assert L.first_difference(got) is None
+    i = 500
+    s, ch = L.streams[i], int(L.out_channels[i])
+    got[L.out_offset[i] + 5 * ch + 1] ^= 0x40; got[L.out_offset[i + 3]] ^= 1
+    d = L.first_difference(got)
+    assert (d.case, d.copy, d.byte, d.pixel) == (s.case.name, s.copy, 5 * ch + 1, 5) and s.case.name in d.text and f"copy {s.copy}" in d.text and "2 bytes differ" in d.text
+    got = L.expected_allocation().copy(); got[L.out_offset[i] + L.out_bytes[i]] = 0        # the first byte behind the image
+    d = L.first_difference(got)
+    assert (d.case, d.copy, d.byte) == (s.case.name, s.copy, int(L.out_bytes[i])) and "gap behind" in d.text
+    got = L.expected_allocation().copy(); got[0] = 0
+    d = L.first_difference(got)
+    assert d.case == L.streams[0].case.name and d.byte == -int(L.out_offset[0]) and "gap in front" in d.text
+    assert L.first_difference(got[:-1]).case is None
+
+
+def test_the_tables_outlive_everything_but_the_layout():
+    """The record of the first attempt at tests/test_qoi_batch_gpu.py, which ended in a host segmentation fault: a pointer taken from a temporary
+    array (`np.array(...).ctypes.data`) names memory numpy has freed by the time the C call reads it.  Here every pointer comes from an attribute of
+    the layout: with nothing alive but the layout, each still reads back as its table."""
+    def make(kind):
+        L = B.resident("one_wave", 3) if kind == "resident" else B.host(3, 0)
+        tables = L.tables()
+        addresses = {name: (C.cast(p, C.c_void_p).value, nbytes) for name, (p, nbytes) in tables.items()}
+        del tables
+        return L, addresses
+    for kind in ("resident", "host"):
+        L, addresses = make(kind)
+        gc.collect()
+        churn = [np.full(1 << 20, 0xEE, np.uint8) for _ in range(8)]; del churn          # (freed memory gets reused)
+        gc.collect()
+        assert set(addresses) >= {"size", "out_offset", "poison", "descs_read"}
+        for name, (address, nbytes) in addresses.items():
+            assert nbytes > 0 and C.string_at(address, nbytes) == getattr(L, name).tobytes(), (kind, name)
+        if kind == "host":
+            for i, s in enumerate(L.streams):
+                assert C.string_at(int(L.ptrs[i]), int(L.size[i])) == s.case.data, s.case.name

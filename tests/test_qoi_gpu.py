@@ -153,8 +153,8 @@ def test_qoi_resident_streams(hip, small_batch_kernel):
 def test_qoi_arbitrary_streams(hip, small_batch_kernel):
     files = _arbitrary_streams()
     # 40 streams: the small-batch kernel of the fixture.  960: the host entry cuts them into launches of 256 (kGroup, qoi.hip), so these run on the
-    # small-batch kernels too -- NOT one wave per stream: k_qoi_decode<1> starts only from the resident entry with at least 768 streams, and no test
-    # sends it these streams yet.  What the 960 cover is a launch per group, each behind its own upload.
+    # small-batch kernels too -- NOT one wave per stream: k_qoi_decode<1> starts only from the resident entry with at least 768 streams, where
+    # tests/test_qoi_batch_gpu.py sends it these streams (and the constructed ones).  What the 960 cover is a launch per group, each behind its own upload.
     for reps in (1, 24):
         blobs = files * reps
         n = len(blobs)
@@ -180,9 +180,8 @@ def test_qoi_large_batches(hip):
     """800 streams in one call.  From host memory (gamut_hip_qoi_decode_batch_device) the files go up in groups of 256 on a copy stream and
     every group is decoded behind its own upload, by a launch of at most 256 streams: the small-batch kernels, never one wave per stream.
     Resident in HBM (gamut_hip_qoi_decode_resident_device) the 800 are one launch, and >= 768 streams run one wave per stream
-    (k_qoi_decode<1>): the only way to that kernel, and these 16 encoder-written images are all the suite sends it -- no stream an
-    encoder would not write (tests/qoi_cases.py has them; nothing runs them on that kernel yet).  Same pixels as the oracle either way,
-    rgba and rgb outputs."""
+    (k_qoi_decode<1>): the only way to that kernel.  These are 16 encoder-written images; the streams no encoder would write
+    (tests/qoi_cases.py) run on that kernel in tests/test_qoi_batch_gpu.py.  Same pixels as the oracle either way, rgba and rgb outputs."""
     rng = np.random.default_rng(9)
     imgs = []
     for k in range(16):
