@@ -220,6 +220,20 @@ extern(C)
     int   gamut_hip_qoix_row_capacity();
     float gamut_hip_qoix_last_decode_kernel_ms();
     float gamut_hip_qoix_last_decode_stage_ms(int stage);
+    // QOIX encode: qoix_lz4_encode as saveQOIX drives it for 8-bit rgb / rgba (plugins/qoix.d:156-339, codecs/qoi2avg.d:376-615,
+    // codecs/lz4.d:289-554), byte for byte.  mode 0: LZ4 when lz4Size + 4 < datalen, 1: always stored.  Deviations: width * channels bytes
+    // of a row are read whatever the pitch is; a bound above 2^31 - 1 is refused.
+    struct gamut_hip_qoix_desc { int width, height, channels, colorspace, mode; float pixel_aspect_ratio, resolution_y; }
+    long  gamut_hip_qoix_encode_bound(const(gamut_hip_qoix_desc)* desc);
+    int   gamut_hip_qoix_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(gamut_hip_qoix_desc)* descs, int count,
+                                             const(long)* out_offset, ubyte* out_, long* out_len, int* status_host, void* stream);
+    void* gamut_hip_qoix_write_to_mem(const(void)* data, int pitch, const(gamut_hip_qoix_desc)* desc, int* out_len);
+    int   gamut_hip_qoix_encode_window();
+    int   gamut_hip_lz4_compress_bound(int n);
+    int   gamut_hip_lz4_compress_batch_device(const(ubyte*)* src, const(int)* len, int count, const(long)* out_offset, ubyte* out_,
+                                              long* out_len, int* status_host, void* stream);
+    float gamut_hip_qoix_last_encode_kernel_ms();
+    float gamut_hip_qoix_last_encode_stage_ms(int stage);
 
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }
@@ -257,6 +271,8 @@ extern(C)
     // (the QOIX struct's numbers are the ones tests/c/qoix_abi_layout.c prints; tests/test_qoix_cpu.py compares them every run.  `version` is a
     //  D keyword: the field is version_ here)
     static assert(48 == gamut_hip_qoix_info.sizeof && 0 == gamut_hip_qoix_info.width.offsetof && 4 == gamut_hip_qoix_info.height.offsetof && 8 == gamut_hip_qoix_info.version_.offsetof && 12 == gamut_hip_qoix_info.channels.offsetof && 16 == gamut_hip_qoix_info.bitdepth.offsetof && 20 == gamut_hip_qoix_info.colorspace.offsetof && 24 == gamut_hip_qoix_info.compression.offsetof && 28 == gamut_hip_qoix_info.pixel_aspect_ratio.offsetof && 32 == gamut_hip_qoix_info.resolution_y.offsetof && 36 == gamut_hip_qoix_info.orig.offsetof && 40 == gamut_hip_qoix_info.pixel_type.offsetof && 44 == gamut_hip_qoix_info.detected.offsetof);
+    // (the QOIX encode struct's numbers are the ones tests/c/qoix_encode_abi_layout.c prints; tests/test_qoix_encode_cpu.py compares them every run)
+    static assert(28 == gamut_hip_qoix_desc.sizeof && 0 == gamut_hip_qoix_desc.width.offsetof && 4 == gamut_hip_qoix_desc.height.offsetof && 8 == gamut_hip_qoix_desc.channels.offsetof && 12 == gamut_hip_qoix_desc.colorspace.offsetof && 16 == gamut_hip_qoix_desc.mode.offsetof && 20 == gamut_hip_qoix_desc.pixel_aspect_ratio.offsetof && 24 == gamut_hip_qoix_desc.resolution_y.offsetof);
     // (the BMP struct's numbers are the ones tests/c/bmp_abi_layout.c prints; tests/test_bmp_cpu.py compares them every run)
     static assert(64 == gamut_hip_bmp_info.sizeof && 0 == gamut_hip_bmp_info.width.offsetof && 4 == gamut_hip_bmp_info.height.offsetof && 8 == gamut_hip_bmp_info.bpp.offsetof && 12 == gamut_hip_bmp_info.header_size.offsetof && 16 == gamut_hip_bmp_info.compression.offsetof && 20 == gamut_hip_bmp_info.channels_in_file.offsetof && 24 == gamut_hip_bmp_info.top_down.offsetof && 28 == gamut_hip_bmp_info.pixel_offset.offsetof && 32 == gamut_hip_bmp_info.palette_size.offsetof && 36 == gamut_hip_bmp_info.mask_r.offsetof && 40 == gamut_hip_bmp_info.mask_g.offsetof && 44 == gamut_hip_bmp_info.mask_b.offsetof && 48 == gamut_hip_bmp_info.mask_a.offsetof && 52 == gamut_hip_bmp_info.pixels_per_meter_x.offsetof && 56 == gamut_hip_bmp_info.pixels_per_meter_y.offsetof && 60 == gamut_hip_bmp_info.pixel_aspect_ratio.offsetof);
     // (the GIF struct's numbers are the ones tests/c/gif_abi_layout.c prints; tests/test_gif_cpu.py compares them every run)

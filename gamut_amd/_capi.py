@@ -63,6 +63,11 @@ class QoixInfo(C.Structure):                                   # gamut_hip_qoix_
                 ("orig", C.c_int32), ("pixel_type", C.c_int32), ("detected", C.c_int32)]
 
 
+class QoixDesc(C.Structure):                                   # gamut_hip_qoix_desc
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("colorspace", C.c_int32), ("mode", C.c_int32),
+                ("pixel_aspect_ratio", C.c_float), ("resolution_y", C.c_float)]
+
+
 class ImageInfo(C.Structure):                                  # gamut_hip_image_info
     _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels_in_file", C.c_int32), ("channels", C.c_int32)]
 
@@ -154,6 +159,15 @@ SIGNATURES = {
     "gamut_hip_qoix_row_capacity": (_i, []),
     "gamut_hip_qoix_last_decode_kernel_ms": (_f, []),
     "gamut_hip_qoix_last_decode_stage_ms": (_f, [_i]),
+    "gamut_hip_qoix_encode_bound": (_i64, [C.POINTER(QoixDesc)]),
+    "gamut_hip_qoix_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(QoixDesc), _i, C.POINTER(_i64), _vp,
+                                            C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_qoix_write_to_mem": (_vp, [_vp, _i, C.POINTER(QoixDesc), _pi]),
+    "gamut_hip_qoix_encode_window": (_i, []),
+    "gamut_hip_lz4_compress_bound": (_i, [_i]),
+    "gamut_hip_lz4_compress_batch_device": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, C.POINTER(_i64), _vp, C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_qoix_last_encode_kernel_ms": (_f, []),
+    "gamut_hip_qoix_last_encode_stage_ms": (_f, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

@@ -951,6 +951,47 @@ int gamut_image_save_tga_to_file(gamut_image* img, const char* path, int flags)
     return ok;
 }
 
+// saveQOIX (plugins/qoix.d:156-242), the 8-bit colour slice: rgb8 / rgba8 / rgbap8 (colorspace 2), layer 0, the image's pixel aspect
+// ratio and vertical DPI in the header, LZ4 when it is smaller; grey and 16-bit types wait for their codecs
+static uint8_t* save_qoix(gamut_image* img, size_t* len)
+{
+    gamut_hip_qoix_desc d{};
+    d.width = img->_width; d.height = img->_height;
+    d.channels = img->_type == GAMUT_PIXEL_rgb8 ? 3 : img->_type == GAMUT_PIXEL_rgba8 || img->_type == GAMUT_PIXEL_rgbap8 ? 4 : 0;
+    d.colorspace = img->_type == GAMUT_PIXEL_rgbap8 ? 2 : 0;
+    d.mode = 0;
+    d.pixel_aspect_ratio = img->_pixelAspectRatio; d.resolution_y = img->_resolutionY;
+    if (!d.channels || img->_layerCount < 1 || gamut_hip_qoix_encode_bound(&d) < 0) return nullptr;
+    if (!img->_device) {
+        int n = 0;
+        uint8_t* r = (uint8_t*)gamut_hip_qoix_write_to_mem(img->_data, (int)img->_pitch, &d, &n);
+        if (r) *len = (size_t)n;
+        return r;
+    }
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
+    return encode_device_image((size_t)gamut_hip_qoix_encode_bound(&d), len, [&](uint8_t* dev, int64_t* n, hipStream_t st) {
+        return gamut_hip_qoix_encode_batch_device(&src, &pitch, &d, 1, &off, dev, n, &status, st);
+    });
+}
+
+uint8_t* gamut_image_save_qoix_to_memory(gamut_image* img, int flags, size_t* len)
+{
+    (void)flags;                                               // saveQOIX ignores them
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
+    return save_qoix(img, len);
+}
+int gamut_image_save_qoix_to_file(gamut_image* img, const char* path, int flags)
+{
+    if (!path) return 0;
+    size_t n = 0;
+    uint8_t* enc = gamut_image_save_qoix_to_memory(img, flags, &n);
+    if (!enc) return 0;
+    const bool ok = write_file(path, enc, n);
+    free(enc);
+    return ok;
+}
+
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980
 {
     (void)flags;                                               // saveQOI, saveJPEG and saveGIF ignore them

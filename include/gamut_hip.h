@@ -655,6 +655,57 @@ int   gamut_hip_qoix_row_capacity(void);
  * decoded or `stage` is out of range */
 float gamut_hip_qoix_last_decode_kernel_ms(void);
 float gamut_hip_qoix_last_decode_stage_ms(int stage);
+/* Encode: byte for byte qoix_lz4_encode (plugins/qoix.d:251-339) as saveQOIX drives it (:156-242) for 8-bit rgb / rgba -- the 25
+ * header bytes, the op stream of qoix_encode (codecs/qoi2avg.d:376-615) with its four 0xff bytes, the LZ4 block of LZ4_compress on a
+ * 64-bit build (codecs/lz4.d:289-554: byU16 below 65547 input bytes, byU32 from there) and the choice between the two files.  Kept
+ * from the reference: px starts at (0, 0, 0, 255); runs cross row ends and end as RUN2 at 1024 pixels or at the last pixel, however
+ * short; the index is a 1024-entry table of positions into a 64-entry FIFO, both zero at first, untouched by a hit; on a miss the
+ * alpha step comes first (ADIFF and a colour op, or RGBA alone); LUMA, LUMA, GRAY, LUMA2, LUMA3, RGB are tried in that order.
+ * Refused, as the reference does: width or height 0, channels outside 3..4, colorspace above 2, height >= 400000000 / width.
+ * Deliberate deviations:
+ *   1. for 4 channels the reference copies pitchBytes into a scanline buffer of 4 * width bytes (a padded pitch overruns it, a
+ *      negative one is a huge memcpy); here width * channels bytes of every row are read, whatever the pitch is;
+ *   2. the reference's int max_size wraps for large shapes; a description whose bound exceeds 2^31 - 1 is refused instead.
+ * Grey (1 or 2 channels) and the 10-bit codecs are not built: refused.
+ * (Declared typedef-first: the layout of this struct is pinned by tests/c/qoix_encode_abi_layout.c and tests/test_qoix_encode_cpu.py.) */
+typedef struct gamut_hip_qoix_desc gamut_hip_qoix_desc;
+struct gamut_hip_qoix_desc {
+    int32_t width, height;
+    int32_t channels;               /* 3 | 4: the SOURCE's channel count, which is the file's */
+    int32_t colorspace;             /* 0..2, header byte 15 (2: premultiplied alpha) */
+    int32_t mode;                   /* 0: the reference's choice, LZ4 when lz4Size + 4 < datalen, else stored; 1: always stored (qoix_encode alone) */
+    float   pixel_aspect_ratio;     /* header bytes 17..20, big-endian, bit for bit (NaN payloads included) */
+    float   resolution_y;           /* header bytes 21..24, likewise */
+};
+/* the bytes a caller must provide for one file: with datalen_max = width * height * (channels + 1) + 4 it is
+ * 29 + datalen_max + datalen_max / 255 + 16 (the stored file and the LZ4 file at LZ4_compressBound); -1 for a refused description
+ * (NULL, the reference's refusals, a mode other than 0 / 1, a bound above 2^31 - 1) */
+int64_t gamut_hip_qoix_encode_bound(const gamut_hip_qoix_desc* desc);
+/* batch: image i is read from DEVICE memory at src[i] (rows src_pitch[i] apart, padded or negative allowed, any alignment) and its
+ * file written to out + out_offset[i] (device, any alignment), which must have gamut_hip_qoix_encode_bound(&descs[i]) bytes; nothing
+ * outside [out_offset[i], out_offset[i] + out_len[i]) is written.  out_len[i] / status_host[i] (host arrays; status_host may be
+ * NULL) are filled when the call returns: a refused image (or a NULL src[i], a negative out_offset[i]) gets
+ * GAMUT_HIP_ERR_INVALID_ARG and out_len 0, the others are still encoded, and the call returns the status of the lowest-numbered
+ * refused image ("image %d:" in last_error).  Three launches, whatever the batch holds: ops, LZ4, the choice. */
+int     gamut_hip_qoix_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_qoix_desc* descs, int count,
+                                           const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host, void* stream);
+/* host drop-in for qoix_lz4_encode: host pixels (rows `pitch` bytes apart, negative allowed) through pinned staging -> malloc'd file
+ * of *out_len bytes, or NULL on refusal (see last_error) */
+void*   gamut_hip_qoix_write_to_mem(const void* data, int pitch, const gamut_hip_qoix_desc* desc, int* out_len);
+/* the op kernel takes this many pixels of the raster per step */
+int     gamut_hip_qoix_encode_window(void);
+/* LZ4_compressBound (n + n / 255 + 16; 0 for n < 0 or n > 0x7E000000), and LZ4_compress for `count` byte strings in DEVICE memory:
+ * string i (src[i], len[i] bytes, any alignment) becomes the LZ4 block at out + out_offset[i], which must have
+ * gamut_hip_lz4_compress_bound(len[i]) bytes; out_len[i] is the block's length, byte for byte what LZ4_compress writes on a 64-bit
+ * build (a length of 0 gives the one-byte block 00).  Refusals (NULL src[i], a length out of range, a negative offset) as in the
+ * image batch.  One launch, a wave per string. */
+int     gamut_hip_lz4_compress_bound(int n);
+int     gamut_hip_lz4_compress_batch_device(const uint8_t* const* src, const int32_t* len, int count, const int64_t* out_offset, uint8_t* out,
+                                            int64_t* out_len, int* status_host, void* stream);
+/* measurements, under GAMUT_HIP_QOIX_TIMING=1 as the decode getters: the GPU milliseconds of the calling thread's last encode call --
+ * all three launches, or one of them (0 ops, 1 LZ4, 2 the choice); -1 when timing is off or nothing was encoded */
+float   gamut_hip_qoix_last_encode_kernel_ms(void);
+float   gamut_hip_qoix_last_encode_stage_ms(int stage);
 
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect

@@ -158,6 +158,13 @@ int      gamut_image_save_bmp_to_file(gamut_image* img, const char* path, int fl
  * state and error are left as they were.  Freed with gamut_free_encoded_image. */
 uint8_t* gamut_image_save_tga_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
 int      gamut_image_save_tga_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
+/* saveQOIX (plugins/qoix.d:156-242; gamut_hip_qoix_encode*), the 8-bit colour slice: rgb8 (3 channels, colorspace 0), rgba8 (4, 0) and
+ * rgbap8 (4, colorspace 2); every other type is refused -- the grey and 16-bit types until their codecs exist on both sides.  Layer 0
+ * of a layered image; pixelAspectRatio and dotsPerInchY go into the header bit for bit; LZ4 when that file is smaller; flags are
+ * ignored.  GAMUT_FORMAT_QOIX (3) is not dispatched from the two generic entries above (they return NULL / 0 for it).  The image's
+ * state and error are left as they were.  Freed with gamut_free_encoded_image. */
+uint8_t* gamut_image_save_qoix_to_memory(gamut_image* img, int flags, size_t* len);     /* NULL (and *len = 0) on refusal */
+int      gamut_image_save_qoix_to_file(gamut_image* img, const char* path, int flags);  /* 1 on success */
 
 #ifdef __cplusplus
 }
