@@ -205,6 +205,15 @@ extern(C)
     int   gamut_hip_tga_encode_window();
     float gamut_hip_tga_last_encode_kernel_ms();
     float gamut_hip_tga_last_encode_stage_ms(int stage);
+    // DDS / BC7 encode: saveDDS (plugins/dds.d:47-216) with bc7enc16_compress_block on its default parameters, byte for byte; comp
+    // is the source's channel count (1 l8, 2 la8, 3 rgb8, 4 rgba8).  Deviation: a file above int.max bytes is refused.
+    long  gamut_hip_dds_encode_bound(int width, int height, int comp);
+    int   gamut_hip_dds_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(int)* width, const(int)* height,
+                                            const(int)* comp, int count, const(long)* out_offset, ubyte* out_, long* out_len,
+                                            int* status_host, void* stream);
+    int   gamut_hip_bc7_encode_blocks_device(const(ubyte)* rgba_tiles, long n, ubyte* out_, void* stream);
+    void* gamut_hip_dds_write_to_mem(const(void)* data, int pitch, int width, int height, int comp, int* out_len);
+    float gamut_hip_dds_last_encode_kernel_ms();
 
     // QOIX, 8-bit rgb / rgba: qoix_lz4_decode (plugins/qoix.d:350-473), LZ4_decompress_fast (codecs/lz4.d:760-978) and qoix_decode
     // (codecs/qoi2avg.d:624-897) on the GPU.  read_header: info.detected is detectQOIX's verdict, the return value the load's

@@ -153,6 +153,11 @@ SIGNATURES = {
     "gamut_hip_tga_encode_window": (_i, []),
     "gamut_hip_tga_last_encode_kernel_ms": (_f, []),
     "gamut_hip_tga_last_encode_stage_ms": (_f, [_i]),
+    "gamut_hip_dds_encode_bound": (_i64, [_i, _i, _i]),
+    "gamut_hip_dds_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), _pi, _pi, _pi, _i, C.POINTER(_i64), _vp, C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_bc7_encode_blocks_device": (_i, [_vp, _i64, _vp, _vp]),
+    "gamut_hip_dds_write_to_mem": (_vp, [_vp, _i, _i, _i, _i, _pi]),
+    "gamut_hip_dds_last_encode_kernel_ms": (_f, []),
     "gamut_hip_qoix_read_header": (_i, [_vp, _sz, C.POINTER(QoixInfo)]),
     "gamut_hip_qoix_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _i, C.POINTER(_i64), _vp, C.POINTER(QoixInfo), _pi, _vp]),
     "gamut_hip_qoix_lz4_decode": (_vp, [_vp, _i, C.POINTER(QoixInfo), _i, _pi]),

@@ -992,6 +992,44 @@ int gamut_image_save_qoix_to_file(gamut_image* img, const char* path, int flags)
     return ok;
 }
 
+// saveDDS (plugins/dds.d:47-216): l8 / la8 / rgb8 / rgba8, scanline(y) of layer 0, BC7 blocks behind a DX10 header
+static uint8_t* save_dds(gamut_image* img, size_t* len)
+{
+    const int comp = img->_type == GAMUT_PIXEL_l8 ? 1 : img->_type == GAMUT_PIXEL_la8 ? 2 : img->_type == GAMUT_PIXEL_rgb8 ? 3 :
+                     img->_type == GAMUT_PIXEL_rgba8 ? 4 : 0;
+    const int w = img->_width, h = img->_height;
+    if (!comp || img->_layerCount < 1 || gamut_hip_dds_encode_bound(w, h, comp) == 0) return nullptr;
+    if (!img->_device) {
+        int n = 0;
+        uint8_t* r = (uint8_t*)gamut_hip_dds_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, &n);
+        if (r) *len = (size_t)n;
+        return r;
+    }
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
+    const int32_t W = w, H = h, Cc = comp;
+    return encode_device_image((size_t)gamut_hip_dds_encode_bound(w, h, comp), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
+        return gamut_hip_dds_encode_batch_device(&src, &pitch, &W, &H, &Cc, 1, &off, d, n, &status, st);
+    });
+}
+
+uint8_t* gamut_image_save_dds_to_memory(gamut_image* img, int flags, size_t* len)
+{
+    (void)flags;                                               // saveDDS ignores them
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
+    return save_dds(img, len);
+}
+int gamut_image_save_dds_to_file(gamut_image* img, const char* path, int flags)
+{
+    if (!path) return 0;
+    size_t n = 0;
+    uint8_t* enc = gamut_image_save_dds_to_memory(img, flags, &n);
+    if (!enc) return 0;
+    const bool ok = write_file(path, enc, n);
+    free(enc);
+    return ok;
+}
+
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980
 {
     (void)flags;                                               // saveQOI, saveJPEG and saveGIF ignore them

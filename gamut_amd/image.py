@@ -36,6 +36,7 @@ IMAGE_SIGNATURES = {
     "gamut_image_save_bmp_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_bmp_to_file": (_i, [_vp, C.c_char_p, _i]),
     "gamut_image_save_tga_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_tga_to_file": (_i, [_vp, C.c_char_p, _i]),
     "gamut_image_save_qoix_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_qoix_to_file": (_i, [_vp, C.c_char_p, _i]),
+    "gamut_image_save_dds_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_dds_to_file": (_i, [_vp, C.c_char_p, _i]),
 }
 _bound = False
 
@@ -56,6 +57,7 @@ LOAD_GREYSCALE, LOAD_ALPHA, LOAD_NO_ALPHA, LOAD_RGB = 0x10000, 0x20000, 0x40000,
 LOAD_8BIT, LOAD_16BIT, LOAD_FP32, LOAD_PREMUL, LOAD_NO_PREMUL = 0x100000, 0x200000, 0x400000, 0x1000000, 0x2000000
 FORMAT_UNKNOWN, FORMAT_JPEG, FORMAT_PNG, FORMAT_QOI = -1, 0, 1, 2
 FORMAT_QOIX = 3                                                # ImageFormat.QOIX: 8-bit rgb / rgba files, read (loadFromMemory) and written (save_qoix_to_memory); save_to_memory(3) returns None
+FORMAT_DDS = 4                                                 # ImageFormat.DDS: written only (save_dds_to_memory), as in the reference; save_to_memory(4) returns None
 FORMAT_GIF = 6                                                 # ImageFormat.GIF: every frame a layer, read and written (rgba8)
 FORMAT_TGA = 5                                                 # ImageFormat.TGA: read (loadFromMemory) and written (save_tga_to_memory); save_to_memory(5) returns None
 FORMAT_BMP = 7                                                 # ImageFormat.BMP (types.d:14-28)
@@ -245,6 +247,21 @@ class Image:
     saveQOIXToMemory = save_qoix_to_memory
 
     def saveQOIXToFile(self, path, flags=0): return bool(self.L.gamut_image_save_qoix_to_file(self.h, str(path).encode(), flags))
+
+    # saveDDS (plugins/dds.d:47-216): l8 / la8 / rgb8 / rgba8 as BC7 blocks, layer 0; flags are ignored
+    def save_dds_to_memory(self, flags=0):
+        """the DDS file as bytes, or None when the image is refused"""
+        n = _sz(0)
+        p = self.L.gamut_image_save_dds_to_memory(self.h, flags, C.byref(n))
+        if not p:
+            return None
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            self.L.gamut_free_encoded_image(p)
+    saveDDSToMemory = save_dds_to_memory
+
+    def saveDDSToFile(self, path, flags=0): return bool(self.L.gamut_image_save_dds_to_file(self.h, str(path).encode(), flags))
 
     @property
     def isDevice(self): return bool(self.L.gamut_image_is_device(self.h))

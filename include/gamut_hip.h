@@ -602,6 +602,37 @@ int     gamut_hip_tga_encode_window(void);
 float   gamut_hip_tga_last_encode_kernel_ms(void);
 float   gamut_hip_tga_last_encode_stage_ms(int stage);
 
+/* ---- DDS / BC7 encode (saveDDS, plugins/dds.d:47-216; bc7enc16_compress_block, codecs/bc7enc16.d) --------------------------------
+ * The file saveDDS writes, byte for byte: "DDS ", DDSURFACEDESC2, DDS_HEADER_DXT10 (148 bytes, DXGI_FORMAT_BC7_UNORM), then one
+ * 16-byte BC7 block per 4 x 4 tile in row-major order, each what bc7enc16_compress_block gives on the parameters of
+ * bc7enc16_compress_block_params_init (64 mode-1 partitions, least squares, partition filterbank, uber level 0, perceptual weights):
+ * mode 6, or mode 1 for an opaque tile where it has the smaller error.  comp is the source's channel count: 1 (l8) -> (v, v, v, 255),
+ * 2 (la8) -> (v, v, v, a), 3 (rgb8) -> (r, g, b, 255), 4 (rgba8); a tile position outside the image is (0, 0, 0, 0), as the
+ * reference's zero-initialised tile has it.  The reference only writes this format; nothing here reads it.
+ * Deliberate deviation: the reference's `int numBlocks` wraps for huge images; a file above 2^31 - 1 bytes is refused here.
+ * The file's size, 148 + 16 * ((width + 3) / 4) * ((height + 3) / 4), or 0 when the image is refused: width or height below 1,
+ * comp outside 1..4, a size above 2^31 - 1. */
+int64_t gamut_hip_dds_encode_bound(int width, int height, int comp);
+/* batch: image i is read from DEVICE memory at src[i] (rows src_pitch[i] apart, negative allowed, any alignment) and written to
+ * out + out_offset[i] (device, any alignment), which must have gamut_hip_dds_encode_bound(...) bytes; nothing outside
+ * [out_offset[i], out_offset[i] + out_len[i]) is written.  out_len[i] / status_host[i] (host arrays; status_host may be NULL) are
+ * filled when the call returns: a refused image (or a NULL src[i], a negative out_offset[i]) gets GAMUT_HIP_ERR_INVALID_ARG and
+ * out_len 0, the others are still encoded, and the call returns the status of the lowest-numbered refused image.  One launch,
+ * whatever the batch holds: a tile is 16 lanes' work and a workgroup serves tiles of any image. */
+int     gamut_hip_dds_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const int32_t* width,
+                                          const int32_t* height, const int32_t* comp, int count, const int64_t* out_offset,
+                                          uint8_t* out, int64_t* out_len, int* status_host, void* stream);
+/* the codec without the container: n tiles of 16 rgba pixels (64 bytes each, DEVICE, any alignment; pixel i of a tile is column
+ * i % 4 of row i / 4) -> n blocks of 16 bytes each (DEVICE, any alignment); n <= 2^31 - 1.  Like the batch call it returns when
+ * the stream has finished the work. */
+int     gamut_hip_bc7_encode_blocks_device(const uint8_t* rgba_tiles, int64_t n, uint8_t* out, void* stream);
+/* host pixels (rows `pitch` bytes apart, negative allowed) through pinned staging -> malloc'd file of *out_len bytes, or NULL on
+ * refusal (see last_error) */
+void*   gamut_hip_dds_write_to_mem(const void* data, int pitch, int width, int height, int comp, int* out_len);
+/* measurements, under GAMUT_HIP_DDS_TIMING=1: the GPU milliseconds of the launch of the calling thread's last dds_encode_batch_device
+ * or bc7_encode_blocks_device call; -1 when timing is off or nothing was encoded */
+float   gamut_hip_dds_last_encode_kernel_ms(void);
+
 /* ---- QOIX, 8-bit rgb / rgba (qoix_lz4_decode, plugins/qoix.d:350-473; LZ4_decompress_fast, codecs/lz4.d:760-978; qoix_decode,
  * codecs/qoi2avg.d:624-897) ------------------------------------------------------------------------------------------------------
  * Decode: every pixel what the reference gives, bit for bit, for files that hold 8-bit rgb or rgba (what saveQOIX writes for rgb8,

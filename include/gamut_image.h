@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ImageFormat (types.d:14-28) */
-enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_QOIX = 3, GAMUT_FORMAT_TGA = 5, GAMUT_FORMAT_GIF = 6, GAMUT_FORMAT_BMP = 7 };   /* ImageFormat, types.d:14-21 */
+enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_QOIX = 3, GAMUT_FORMAT_DDS = 4, GAMUT_FORMAT_TGA = 5, GAMUT_FORMAT_GIF = 6, GAMUT_FORMAT_BMP = 7 };   /* ImageFormat, types.d:14-21 */
 
 /* LoadFlags (types.d:139-197) */
 enum {
@@ -165,6 +165,12 @@ int      gamut_image_save_tga_to_file(gamut_image* img, const char* path, int fl
  * state and error are left as they were.  Freed with gamut_free_encoded_image. */
 uint8_t* gamut_image_save_qoix_to_memory(gamut_image* img, int flags, size_t* len);     /* NULL (and *len = 0) on refusal */
 int      gamut_image_save_qoix_to_file(gamut_image* img, const char* path, int flags);  /* 1 on success */
+/* saveDDS (plugins/dds.d:47-216; gamut_hip_dds_encode*): l8 / la8 / rgb8 / rgba8 as BC7 blocks behind a DX10 header; every other type
+ * is refused, lap8 and rgbap8 included (saveDDS's switch has no case for them).  Layer 0 of a layered image; flags are ignored.
+ * GAMUT_FORMAT_DDS (4) is not dispatched from the two generic entries above (they return NULL / 0 for it), and no DDS file is
+ * identified or loaded, as in the reference.  The image's state and error are left as they were.  Freed with gamut_free_encoded_image. */
+uint8_t* gamut_image_save_dds_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
+int      gamut_image_save_dds_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
 
 #ifdef __cplusplus
 }
