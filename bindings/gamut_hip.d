@@ -195,6 +195,19 @@ extern(C)
                                             ubyte* out_, gamut_hip_tga_info* info, int* status_host, void* stream);
     int   gamut_hip_tga_rle_window();
     float gamut_hip_tga_last_decode_kernel_ms();
+    // SQZ decode (SQZ_decode codecs/sqz.d:2253-2296, loadSQZ plugins/sqz.d:43-133).  decode_coeffs is the bit-serial front end on the host
+    // (coefficients as the reference holds them after SQZ_decode_round_coefficients: sign-magnitude, bit 0 the sign), reconstruct_batch_device
+    // the back end on the GPU (IDWT and colour; `coeffs` is a working buffer, unspecified after the call), decode_batch_device both from files.
+    struct gamut_hip_sqz_info { int width, height, planes, color_mode, levels, scan_order, subsampling, pixel_type, detected; }
+    struct gamut_hip_sqz_desc { int width, height, color_mode, levels; long coeff_offset; }
+    int   gamut_hip_sqz_read_header(const(ubyte)* data, size_t len, gamut_hip_sqz_info* info);
+    int   gamut_hip_sqz_decode_coeffs(const(ubyte)* data, size_t len, short* planes, size_t capacity, gamut_hip_sqz_info* info);
+    int   gamut_hip_sqz_reconstruct_batch_device(const(short)* coeffs, const(gamut_hip_sqz_desc)* descs, int count, const(long)* out_offset,
+                                                 ubyte* out_, int* status_host, void* stream);
+    int   gamut_hip_sqz_decode_batch_device(const(ubyte*)* data, const(size_t)* len, int count, const(long)* out_offset, ubyte* out_,
+                                            gamut_hip_sqz_info* info, int* status_host, void* stream);
+    const(ubyte)* gamut_hip_sqz_linear_to_srgb_table();
+    float gamut_hip_sqz_last_decode_stage_ms(int stage);
     // TGA encode: TGAEncoder as saveTGA drives it (codecs/tga.d:57-281, plugins/tga.d:128-150), byte for byte; comp is the source's
     // channel count (1 l8, 2 la8, 3 rgb8, 4 rgba8).  Deviations: width or height 0 and a bound above int.max are refused.
     long  gamut_hip_tga_encode_bound(int width, int height, int comp);
@@ -280,6 +293,9 @@ extern(C)
     // (the QOIX struct's numbers are the ones tests/c/qoix_abi_layout.c prints; tests/test_qoix_cpu.py compares them every run.  `version` is a
     //  D keyword: the field is version_ here)
     static assert(48 == gamut_hip_qoix_info.sizeof && 0 == gamut_hip_qoix_info.width.offsetof && 4 == gamut_hip_qoix_info.height.offsetof && 8 == gamut_hip_qoix_info.version_.offsetof && 12 == gamut_hip_qoix_info.channels.offsetof && 16 == gamut_hip_qoix_info.bitdepth.offsetof && 20 == gamut_hip_qoix_info.colorspace.offsetof && 24 == gamut_hip_qoix_info.compression.offsetof && 28 == gamut_hip_qoix_info.pixel_aspect_ratio.offsetof && 32 == gamut_hip_qoix_info.resolution_y.offsetof && 36 == gamut_hip_qoix_info.orig.offsetof && 40 == gamut_hip_qoix_info.pixel_type.offsetof && 44 == gamut_hip_qoix_info.detected.offsetof);
+    // (the SQZ structs' numbers are the ones tests/c/sqz_abi_layout.c prints; tests/test_sqz_cpu.py compares them every run)
+    static assert(36 == gamut_hip_sqz_info.sizeof && 0 == gamut_hip_sqz_info.width.offsetof && 4 == gamut_hip_sqz_info.height.offsetof && 8 == gamut_hip_sqz_info.planes.offsetof && 12 == gamut_hip_sqz_info.color_mode.offsetof && 16 == gamut_hip_sqz_info.levels.offsetof && 20 == gamut_hip_sqz_info.scan_order.offsetof && 24 == gamut_hip_sqz_info.subsampling.offsetof && 28 == gamut_hip_sqz_info.pixel_type.offsetof && 32 == gamut_hip_sqz_info.detected.offsetof);
+    static assert(24 == gamut_hip_sqz_desc.sizeof && 0 == gamut_hip_sqz_desc.width.offsetof && 4 == gamut_hip_sqz_desc.height.offsetof && 8 == gamut_hip_sqz_desc.color_mode.offsetof && 12 == gamut_hip_sqz_desc.levels.offsetof && 16 == gamut_hip_sqz_desc.coeff_offset.offsetof);
     // (the QOIX encode struct's numbers are the ones tests/c/qoix_encode_abi_layout.c prints; tests/test_qoix_encode_cpu.py compares them every run)
     static assert(28 == gamut_hip_qoix_desc.sizeof && 0 == gamut_hip_qoix_desc.width.offsetof && 4 == gamut_hip_qoix_desc.height.offsetof && 8 == gamut_hip_qoix_desc.channels.offsetof && 12 == gamut_hip_qoix_desc.colorspace.offsetof && 16 == gamut_hip_qoix_desc.mode.offsetof && 20 == gamut_hip_qoix_desc.pixel_aspect_ratio.offsetof && 24 == gamut_hip_qoix_desc.resolution_y.offsetof);
     // (the BMP struct's numbers are the ones tests/c/bmp_abi_layout.c prints; tests/test_bmp_cpu.py compares them every run)

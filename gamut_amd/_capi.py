@@ -68,6 +68,14 @@ class QoixDesc(C.Structure):                                   # gamut_hip_qoix_
                 ("pixel_aspect_ratio", C.c_float), ("resolution_y", C.c_float)]
 
 
+class SqzInfo(C.Structure):                                    # gamut_hip_sqz_info
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "planes", "color_mode", "levels", "scan_order", "subsampling", "pixel_type", "detected")]
+
+
+class SqzDesc(C.Structure):                                    # gamut_hip_sqz_desc
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color_mode", C.c_int32), ("levels", C.c_int32), ("coeff_offset", C.c_int64)]
+
+
 class ImageInfo(C.Structure):                                  # gamut_hip_image_info
     _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels_in_file", C.c_int32), ("channels", C.c_int32)]
 
@@ -173,6 +181,12 @@ SIGNATURES = {
     "gamut_hip_lz4_compress_batch_device": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, C.POINTER(_i64), _vp, C.POINTER(_i64), _pi, _vp]),
     "gamut_hip_qoix_last_encode_kernel_ms": (_f, []),
     "gamut_hip_qoix_last_encode_stage_ms": (_f, [_i]),
+    "gamut_hip_sqz_read_header": (_i, [_vp, _sz, C.POINTER(SqzInfo)]),
+    "gamut_hip_sqz_decode_coeffs": (_i, [_vp, _sz, _vp, _sz, C.POINTER(SqzInfo)]),
+    "gamut_hip_sqz_reconstruct_batch_device": (_i, [_vp, C.POINTER(SqzDesc), _i, C.POINTER(_i64), _vp, _pi, _vp]),
+    "gamut_hip_sqz_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, C.POINTER(_i64), _vp, C.POINTER(SqzInfo), _pi, _vp]),
+    "gamut_hip_sqz_linear_to_srgb_table": (_vp, []),
+    "gamut_hip_sqz_last_decode_stage_ms": (_f, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

@@ -24,6 +24,7 @@ using namespace gamut;
 
 const char* const kStrImageHasNoType           = "Image has no type";
 const char* const kStrImageDecodingFailed      = "Image decoding failed";
+const char* const kStrImageDecodingIOFailure   = "I/O failure while decoding image";
 const char* const kStrImageFormatUnidentified  = "Unidentified image format";
 const char* const kStrImageNotInitialized      = "Uninitialized image";
 const char* const kStrImageTooLarge            = "Can't have an image that exceeds Gamut size limitations";
@@ -521,6 +522,26 @@ struct gamut_image {
         adopt(decoded, hd.width, hd.height, kType8[comps], comps, -1.0f, -1.0f);                // :87-88 GAMUT_UNKNOWN_ASPECT_RATIO / _RESOLUTION
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);                           // :94
     }
+    void loadSQZ(const uint8_t* bytes, size_t len, int flags)                               // plugins/sqz.d:43-133
+    {
+        gamut_hip_sqz_info hd, info;
+        // the sizing call :80-85: SQZ_decode_header and SQZ_validate_input; anything but SQZ_BUFFER_TOO_SMALL is an I/O failure
+        if (gamut_hip_sqz_read_header(bytes, len, &hd) != GAMUT_HIP_OK) { error(kStrImageDecodingIOFailure); return; }
+        const size_t nbytes = (size_t)hd.width * hd.height * hd.planes;
+        if (hd.width > MAX_W || hd.height > MAX_H || (long long)nbytes > MAX_BYTES) { error(kStrImageTooLarge); return; }      // :88-94 (16-bit sides never get here)
+        // the decode is the GPU's either way: a device image keeps the allocation (its rows are tight), a host image gets the pixels copied back
+        uint8_t* dev = dmalloc(nbytes);
+        const int64_t zero = 0; int st = 0;
+        if (!dev || gamut_hip_sqz_decode_batch_device(&bytes, &len, 1, &zero, dev, &info, &st, nullptr) != GAMUT_HIP_OK) {          // :112-118
+            if (dev) (void)hipFree(dev);
+            error(kStrImageDecodingIOFailure); return;
+        }
+        uint8_t* decoded = residentOrHostCopy(dev, nbytes);
+        if (!decoded) { error(kStrImageDecodingIOFailure); return; }
+        adopt(decoded, hd.width, hd.height, hd.pixel_type, hd.planes, -1.0f, -1.0f);            // :120-129 l8 / rgb8, GAMUT_UNKNOWN_ASPECT_RATIO / _RESOLUTION
+        _layoutConstraints = 0;                                                             // :127
+        convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);                           // :132
+    }
     // Layers of tight top-down rgba8 rows (device memory) into the image's own storage, whatever pitch and layer offset its constraints gave it
     bool fillLayersFromDevice(const uint8_t* dev, size_t layerBytes, size_t rowBytes)
     {
@@ -567,6 +588,7 @@ static int identify(const uint8_t* b, size_t len)
     if (b && len >= 4 && !memcmp(b, "qoix", 4)) return GAMUT_FORMAT_QOIX;                   // detectQOIX plugins/qoix.d:149-153 ('o' cannot be a TGA colour-map type)
     if (b && len >= 6 && (!memcmp(b, "GIF87a", 6) || !memcmp(b, "GIF89a", 6))) return GAMUT_FORMAT_GIF;   // detectGIF plugins/gif.d:42-53
     if (gamut_hip_identify_format(b, len) == GAMUT_HIP_FORMAT_BMP) return GAMUT_FORMAT_BMP;  // detectBMP plugins/bmp.d:45-82
+    if (b && len >= 1 && b[0] == 0xA5) return GAMUT_FORMAT_SQZ;                             // detectSQZ plugins/sqz.d:135-139: one byte; by format number behind BMP, before TGA
     if (gamut_hip_identify_format(b, len) == GAMUT_HIP_FORMAT_TGA) return GAMUT_FORMAT_TGA;  // detectTGA plugins/tga.d:97-126, last (image.d:1056)
     return GAMUT_FORMAT_unknown;
 }
@@ -620,6 +642,7 @@ int gamut_image_load_from_memory(gamut_image* img, const uint8_t* bytes, size_t 
     case GAMUT_FORMAT_BMP:  img->loadBMP(bytes, len, flags); break;
     case GAMUT_FORMAT_GIF:  img->loadGIF(bytes, len, flags); break;
     case GAMUT_FORMAT_TGA:  img->loadTGA(bytes, len, flags); break;
+    case GAMUT_FORMAT_SQZ:  img->loadSQZ(bytes, len, flags); break;
     default: img->error(kStrImageFormatUnidentified); break;
     }
     return img->isValid();

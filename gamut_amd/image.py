@@ -60,6 +60,7 @@ FORMAT_QOIX = 3                                                # ImageFormat.QOI
 FORMAT_DDS = 4                                                 # ImageFormat.DDS: written only (save_dds_to_memory), as in the reference; save_to_memory(4) returns None
 FORMAT_GIF = 6                                                 # ImageFormat.GIF: every frame a layer, read and written (rgba8)
 FORMAT_TGA = 5                                                 # ImageFormat.TGA: read (loadFromMemory) and written (save_tga_to_memory); save_to_memory(5) returns None
+FORMAT_SQZ = 9                                                 # ImageFormat.SQZ: read only (loadFromMemory): l8 / rgb8; save_to_memory(9) returns None
 FORMAT_BMP = 7                                                 # ImageFormat.BMP (types.d:14-28)
 ENCODE_PNG_COMPRESSION_DEFAULT, ENCODE_PNG_COMPRESSION_FAST, ENCODE_PNG_COMPRESSION_SMALL = 0, 2, 10                # types.d:220-248
 (ENCODE_PNG_COMPRESSION_0, ENCODE_PNG_COMPRESSION_1, ENCODE_PNG_COMPRESSION_2, ENCODE_PNG_COMPRESSION_3, ENCODE_PNG_COMPRESSION_4,

@@ -602,6 +602,63 @@ int     gamut_hip_tga_encode_window(void);
 float   gamut_hip_tga_last_encode_kernel_ms(void);
 float   gamut_hip_tga_last_encode_stage_ms(int stage);
 
+/* ---- SQZ decode (SQZ_decode, codecs/sqz.d; loadSQZ / detectSQZ, plugins/sqz.d) ----------------------------------------------------
+ * SQZ is an embedded wavelet coder: a 6-byte header, then ONE bit stream that may be cut anywhere (every prefix of at least 7 bytes
+ * of a good file is a good file).  The decoder has two halves.  The FRONT END (host threads, gamut_hip_sqz_decode_coeffs) walks the
+ * bit stream -- WDR bit planes over linked lists per subband, interleaved by a schedule -- and leaves the reference's coefficient
+ * buffer as it stands after SQZ_decode_round_coefficients.  The BACK END (HIP kernels, gamut_hip_sqz_reconstruct_batch_device) is
+ * SQZ_dwt_convert_from_sign_magnitude, SQZ_idwt (up to eight levels of the in-place 5/3 integer IDWT per plane) and one of the four
+ * inverse colour transforms (grey, YCoCg-R, integer Oklab, LOG-L1), bit for bit.  Encoding (saveSQZ) is not provided.
+ * Refusals the reference does not have: an allocation that cannot be had (GAMUT_HIP_ERR_OUT_OF_MEMORY).  Nothing else deviates.
+ * (Declared typedef-first: the layout of both structs is pinned by tests/c/sqz_abi_layout.c and tests/test_sqz_cpu.py.) */
+typedef struct gamut_hip_sqz_info gamut_hip_sqz_info;
+struct gamut_hip_sqz_info {
+    int32_t width, height;          /* 8..65535 each */
+    int32_t planes;                 /* 1 (colour mode 0) or 3 */
+    int32_t color_mode;             /* 0 grey, 1 YCoCg-R, 2 Oklab, 3 LOG-L1 */
+    int32_t levels;                 /* 1..8 DWT levels, at most ilog2(min side) - 3 with ilog2 = index of the top bit + 1 */
+    int32_t scan_order;             /* 0 raster, 1 snake, 2 Morton, 3 Hilbert */
+    int32_t subsampling;            /* 0 / 1: chroma planes scheduled one round later */
+    int32_t pixel_type;             /* PixelType of the decoded image: 0 = l8, 9 = rgb8 */
+    int32_t detected;               /* detectSQZ's verdict: the first byte is 0xA5 */
+};
+/* one image of a reconstruction batch */
+typedef struct gamut_hip_sqz_desc gamut_hip_sqz_desc;
+struct gamut_hip_sqz_desc {
+    int32_t width, height, color_mode, levels;   /* as in gamut_hip_sqz_info; planes follows from color_mode */
+    int64_t coeff_offset;           /* where this image's planes begin in `coeffs`, counted in int16 elements, >= 0 */
+};
+/* the header alone (host, no GPU needed): GAMUT_HIP_OK, or GAMUT_HIP_ERR_DECODE where SQZ_decode_header / SQZ_validate_input refuse
+ * (wrong magic, fewer than 7 bytes, a side outside 8..65535, more levels than the size admits).  Fields are filled on success;
+ * `detected` always. */
+int gamut_hip_sqz_read_header(const uint8_t* data, size_t len, gamut_hip_sqz_info* info);
+/* the front end (host, no GPU needed): planes * width * height coefficients exactly as the reference holds them after
+ * SQZ_decode_round_coefficients -- sign-magnitude, bit 0 the sign, planes one after another, subbands interleaved in place -- into
+ * planes[0 .. capacity).  A capacity below planes * width * height is GAMUT_HIP_ERR_INVALID_ARG (info is filled: ask with capacity 0). */
+int gamut_hip_sqz_decode_coeffs(const uint8_t* data, size_t len, int16_t* planes, size_t capacity, gamut_hip_sqz_info* info);
+/* the back end: `count` images whose coefficient planes are resident in device memory at coeffs + descs[i].coeff_offset ->
+ * tight rows of width * planes bytes (l8 or rgb8) at out + out_offset[i] (device, any byte alignment).  descs, out_offset and
+ * status_host are host arrays; status_host may be NULL.  `coeffs` is a WORKING buffer: its contents after the call are unspecified.
+ * An image whose desc is refused (geometry that gamut_hip_sqz_read_header would refuse, a negative offset) gets
+ * GAMUT_HIP_ERR_INVALID_ARG and writes nothing, the others are reconstructed, and the call returns the status of the lowest-numbered
+ * refused image ("image %d: ...").  One launch per DWT level -- as many as the deepest image of the batch has, at most eight,
+ * whatever the number of images; the last one does the colour transform as well.  Nothing outside an image's own width * height *
+ * planes bytes is written.  Returns when the pixels are in place. */
+int gamut_hip_sqz_reconstruct_batch_device(const int16_t* coeffs, const gamut_hip_sqz_desc* descs, int count, const int64_t* out_offset,
+                                           uint8_t* out, int* status_host, void* stream);
+/* `count` SQZ files in host memory -> pixels as above.  Headers are parsed, the front end runs on the library's host worker pool (at
+ * most 16 threads), the coefficients are staged in pinned memory and uploaded, the back end follows.  info[i] / status_host[i] (host
+ * arrays, either may be NULL) are filled when the call returns; a refused file gets GAMUT_HIP_ERR_DECODE and writes nothing, its
+ * neighbours are decoded, and the call returns the status of the lowest-numbered refused file ("image %d: ..."). */
+int gamut_hip_sqz_decode_batch_device(const uint8_t* const* data, const size_t* len, int count, const int64_t* out_offset, uint8_t* out,
+                                      gamut_hip_sqz_info* info, int* status_host, void* stream);
+/* SQZ_linear_to_sRGB (codecs/sqz.d:1287-1321): 512 bytes, generated from the sRGB transfer function (every entry reproduced) */
+const uint8_t* gamut_hip_sqz_linear_to_srgb_table(void);
+/* measurements: with GAMUT_HIP_SQZ_TIMING=1 the calls bracket their stages with events / clocks; milliseconds of the calling thread's
+ * last call -- 0: the back end's kernels (GPU time), 1: the host front end of the file-level call (wall clock), 2: staging copy and
+ * upload (wall clock until the upload is queued); -1 when timing is off, nothing was decoded or `stage` is out of range */
+float gamut_hip_sqz_last_decode_stage_ms(int stage);
+
 /* ---- DDS / BC7 encode (saveDDS, plugins/dds.d:47-216; bc7enc16_compress_block, codecs/bc7enc16.d) --------------------------------
  * The file saveDDS writes, byte for byte: "DDS ", DDSURFACEDESC2, DDS_HEADER_DXT10 (148 bytes, DXGI_FORMAT_BC7_UNORM), then one
  * 16-byte BC7 block per 4 x 4 tile in row-major order, each what bc7enc16_compress_block gives on the parameters of

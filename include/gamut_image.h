@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ImageFormat (types.d:14-28) */
-enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_QOIX = 3, GAMUT_FORMAT_DDS = 4, GAMUT_FORMAT_TGA = 5, GAMUT_FORMAT_GIF = 6, GAMUT_FORMAT_BMP = 7 };   /* ImageFormat, types.d:14-21 */
+enum { GAMUT_FORMAT_unknown = -1, GAMUT_FORMAT_JPEG = 0, GAMUT_FORMAT_PNG = 1, GAMUT_FORMAT_QOI = 2, GAMUT_FORMAT_QOIX = 3, GAMUT_FORMAT_DDS = 4, GAMUT_FORMAT_TGA = 5, GAMUT_FORMAT_GIF = 6, GAMUT_FORMAT_BMP = 7, GAMUT_FORMAT_SQZ = 9 };   /* ImageFormat, types.d:14-21 */
 
 /* LoadFlags (types.d:139-197) */
 enum {
