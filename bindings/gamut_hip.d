@@ -208,6 +208,20 @@ extern(C)
                                             gamut_hip_sqz_info* info, int* status_host, void* stream);
     const(ubyte)* gamut_hip_sqz_linear_to_srgb_table();
     float gamut_hip_sqz_last_decode_stage_ms(int stage);
+    // SQZ encode (SQZ_encode codecs/sqz.d:2208-2240, saveSQZ plugins/sqz.d:141-201).  analyze_batch_device is the front half on the GPU (colour
+    // transform, DWT, sign-magnitude: the coefficient buffer reconstruct_batch_device consumes), dwt_batch_device the same fed with int16
+    // planes, encode_coeffs the bit-plane writer on the host, encode_batch_device both: device pixels -> files in HOST memory.
+    struct gamut_hip_sqz_encode_desc { int width, height, color_mode, levels, scan_order, subsampling; long budget; }
+    long  gamut_hip_sqz_budget_from_flags(int width, int height, int flags);
+    int   gamut_hip_sqz_analyze_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(gamut_hip_sqz_encode_desc)* descs, int count,
+                                             short* coeffs, const(long)* coeff_offset, int* status_host, void* stream);
+    int   gamut_hip_sqz_dwt_batch_device(const(short)* planes_in, const(gamut_hip_sqz_encode_desc)* descs, int count, short* coeffs,
+                                         const(long)* coeff_offset, int* status_host, void* stream);
+    int   gamut_hip_sqz_encode_coeffs(const(short)* planes, const(gamut_hip_sqz_encode_desc)* desc, ubyte* dst, long* len);
+    int   gamut_hip_sqz_encode_batch_device(const(ubyte*)* src, const(long)* src_pitch, const(gamut_hip_sqz_encode_desc)* descs, int count,
+                                            const(long)* out_offset, ubyte* out_, long* out_len, int* status_host, void* stream);
+    void* gamut_hip_sqz_write_to_mem(const(void)* data, int pitch, const(gamut_hip_sqz_encode_desc)* desc, int* out_len);
+    float gamut_hip_sqz_last_encode_stage_ms(int stage);
     // TGA encode: TGAEncoder as saveTGA drives it (codecs/tga.d:57-281, plugins/tga.d:128-150), byte for byte; comp is the source's
     // channel count (1 l8, 2 la8, 3 rgb8, 4 rgba8).  Deviations: width or height 0 and a bound above int.max are refused.
     long  gamut_hip_tga_encode_bound(int width, int height, int comp);
@@ -296,6 +310,8 @@ extern(C)
     // (the SQZ structs' numbers are the ones tests/c/sqz_abi_layout.c prints; tests/test_sqz_cpu.py compares them every run)
     static assert(36 == gamut_hip_sqz_info.sizeof && 0 == gamut_hip_sqz_info.width.offsetof && 4 == gamut_hip_sqz_info.height.offsetof && 8 == gamut_hip_sqz_info.planes.offsetof && 12 == gamut_hip_sqz_info.color_mode.offsetof && 16 == gamut_hip_sqz_info.levels.offsetof && 20 == gamut_hip_sqz_info.scan_order.offsetof && 24 == gamut_hip_sqz_info.subsampling.offsetof && 28 == gamut_hip_sqz_info.pixel_type.offsetof && 32 == gamut_hip_sqz_info.detected.offsetof);
     static assert(24 == gamut_hip_sqz_desc.sizeof && 0 == gamut_hip_sqz_desc.width.offsetof && 4 == gamut_hip_sqz_desc.height.offsetof && 8 == gamut_hip_sqz_desc.color_mode.offsetof && 12 == gamut_hip_sqz_desc.levels.offsetof && 16 == gamut_hip_sqz_desc.coeff_offset.offsetof);
+    // (the SQZ encode struct's numbers are the ones tests/c/sqz_encode_abi_layout.c prints; tests/test_sqz_encode_cpu.py compares them every run)
+    static assert(32 == gamut_hip_sqz_encode_desc.sizeof && 0 == gamut_hip_sqz_encode_desc.width.offsetof && 4 == gamut_hip_sqz_encode_desc.height.offsetof && 8 == gamut_hip_sqz_encode_desc.color_mode.offsetof && 12 == gamut_hip_sqz_encode_desc.levels.offsetof && 16 == gamut_hip_sqz_encode_desc.scan_order.offsetof && 20 == gamut_hip_sqz_encode_desc.subsampling.offsetof && 24 == gamut_hip_sqz_encode_desc.budget.offsetof);
     // (the QOIX encode struct's numbers are the ones tests/c/qoix_encode_abi_layout.c prints; tests/test_qoix_encode_cpu.py compares them every run)
     static assert(28 == gamut_hip_qoix_desc.sizeof && 0 == gamut_hip_qoix_desc.width.offsetof && 4 == gamut_hip_qoix_desc.height.offsetof && 8 == gamut_hip_qoix_desc.channels.offsetof && 12 == gamut_hip_qoix_desc.colorspace.offsetof && 16 == gamut_hip_qoix_desc.mode.offsetof && 20 == gamut_hip_qoix_desc.pixel_aspect_ratio.offsetof && 24 == gamut_hip_qoix_desc.resolution_y.offsetof);
     // (the BMP struct's numbers are the ones tests/c/bmp_abi_layout.c prints; tests/test_bmp_cpu.py compares them every run)

@@ -76,6 +76,11 @@ class SqzDesc(C.Structure):                                    # gamut_hip_sqz_d
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color_mode", C.c_int32), ("levels", C.c_int32), ("coeff_offset", C.c_int64)]
 
 
+class SqzEncodeDesc(C.Structure):                              # gamut_hip_sqz_encode_desc
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("color_mode", C.c_int32), ("levels", C.c_int32), ("scan_order", C.c_int32),
+                ("subsampling", C.c_int32), ("budget", C.c_int64)]
+
+
 class ImageInfo(C.Structure):                                  # gamut_hip_image_info
     _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels_in_file", C.c_int32), ("channels", C.c_int32)]
 
@@ -187,6 +192,14 @@ SIGNATURES = {
     "gamut_hip_sqz_decode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, C.POINTER(_i64), _vp, C.POINTER(SqzInfo), _pi, _vp]),
     "gamut_hip_sqz_linear_to_srgb_table": (_vp, []),
     "gamut_hip_sqz_last_decode_stage_ms": (_f, [_i]),
+    "gamut_hip_sqz_budget_from_flags": (_i64, [_i, _i, _i]),
+    "gamut_hip_sqz_analyze_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(SqzEncodeDesc), _i, _vp, C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_sqz_dwt_batch_device": (_i, [_vp, C.POINTER(SqzEncodeDesc), _i, _vp, C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_sqz_encode_coeffs": (_i, [_vp, C.POINTER(SqzEncodeDesc), _vp, C.POINTER(_i64)]),
+    "gamut_hip_sqz_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(SqzEncodeDesc), _i, C.POINTER(_i64), _vp,
+                                           C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_sqz_write_to_mem": (_vp, [_vp, _i, C.POINTER(SqzEncodeDesc), _pi]),
+    "gamut_hip_sqz_last_encode_stage_ms": (_f, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

@@ -1053,6 +1053,47 @@ int gamut_image_save_dds_to_file(gamut_image* img, const char* path, int flags)
     return ok;
 }
 
+// saveSQZ (plugins/sqz.d:141-201): rgb8 only, sides of at least 8, scanptr(0) of layer 0; Oklab, 7 levels (clamped to what the size
+// admits), chroma one round later, snake scan; the byte budget comes from the flags and the file is the bytes used, not the budget
+static uint8_t* save_sqz(gamut_image* img, int flags, size_t* len)
+{
+    const int w = img->_width, h = img->_height;
+    if (w < 8 || h < 8 || w > 65535 || h > 65535 || img->_type != GAMUT_PIXEL_rgb8 || img->_layerCount < 1) return nullptr;
+    gamut_hip_sqz_encode_desc d{};
+    d.width = w; d.height = h; d.color_mode = 2; d.levels = 7; d.scan_order = 1; d.subsampling = 1;
+    d.budget = gamut_hip_sqz_budget_from_flags(w, h, flags);
+    if (!img->_device) {
+        int n = 0;
+        uint8_t* r = (uint8_t*)gamut_hip_sqz_write_to_mem(img->_data, (int)img->_pitch, &d, &n);
+        if (r) *len = (size_t)n;
+        return r;
+    }
+    uint8_t* file = (uint8_t*)malloc((size_t)d.budget);               // the writer runs on the host: the file never is in device memory
+    if (!file) return nullptr;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    if (gamut_hip_sqz_encode_batch_device(&src, &pitch, &d, 1, &off, file, &n, &status, nullptr) != GAMUT_HIP_OK) { free(file); return nullptr; }
+    if (void* shrunk = realloc(file, (size_t)n)) file = (uint8_t*)shrunk;
+    *len = (size_t)n;
+    return file;
+}
+
+uint8_t* gamut_image_save_sqz_to_memory(gamut_image* img, int flags, size_t* len)
+{
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
+    return save_sqz(img, flags, len);
+}
+int gamut_image_save_sqz_to_file(gamut_image* img, const char* path, int flags)
+{
+    if (!path) return 0;
+    size_t n = 0;
+    uint8_t* enc = gamut_image_save_sqz_to_memory(img, flags, &n);
+    if (!enc) return 0;
+    const bool ok = write_file(path, enc, n);
+    free(enc);
+    return ok;
+}
+
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980
 {
     (void)flags;                                               // saveQOI, saveJPEG and saveGIF ignore them

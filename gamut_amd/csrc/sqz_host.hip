@@ -1,5 +1,6 @@
 // sqz_host.hip -- the SQZ front end on the host: SQZ_decode (source/gamut/codecs/sqz.d:2253-2296) restated up to and including
-// SQZ_decode_round_coefficients (:2082-2103).  Host code only: no device is needed or touched.
+// SQZ_decode_round_coefficients (:2082-2103), and the back half of SQZ_encode (:2208-2240): SQZ_encode_header and SQZ_schedule_task over
+// the coefficient buffer the GPU's front half (sqz_encode.hip) leaves.  Host code only: no device is needed or touched.
 //
 // SQZ is an embedded bit-plane coder (WDR: wavelet difference reduction): ONE bit stream, three linked lists per subband (LIP
 // insignificant, NSP newly significant, LSP significant) and a scheduler that interleaves the subbands round by round.  Nothing in
@@ -259,9 +260,9 @@ int schedule(int mode, int plane, int level, int o)
     return o == 0 ? 0 : first[o] + level + 1;
 }
 
-struct Decoder {
+// What SQZ_encode and SQZ_decode share: the context, the band layout, a band's LIP in scan order and the scheduler's walk.
+struct Coder {
     Band band[3][kMaxLevel][kBands];
-    BitReader in;
     int16_t* data = nullptr;
     size_t width = 0, height = 0, levels = 0, planes = 0;
     int mode = 0, scan = 0, subsampling = 0;
@@ -285,7 +286,7 @@ struct Decoder {
             }
         }
     }
-    bool init_band(Band& b)                                         // SQZ_scan_init + SQZ_decode_init_subband :1124-1139, :1890-1899
+    bool init_lists(Band& b)                                        // SQZ_common_init_subband :1850-1864 with SQZ_scan_init :1124-1139
     {
         b.capacity = b.width * b.height; b.used = 0;
         free(b.nodes);
@@ -298,6 +299,50 @@ struct Decoder {
         case 2: { Morton s(b.width, b.height); fill_lip(b, s); break; }
         default: { Hilbert s(b.width, b.height); fill_lip(b, s); break; }
         }
+        return true;
+    }
+    // SQZ_schedule_task :2105-2168.  task(band, first visit) > 0: go on; 0: the stream is at its end; < 0: give up, and that is the result
+    template <class AtEnd, class Task> int walk(AtEnd at_end, Task task)
+    {
+        size_t state = 0, plane = 0, level = 0, o = 0;
+        int round = 0; bool done = false;
+        while (!done && !at_end()) {
+            done = true;
+            for (;;) {
+                Band& b = band[plane][level][o];
+                if (round < b.round || (round > b.round && b.bitplane == 0)) done = done && round > b.round;
+                else {
+                    const int r = task(b, b.round == round);
+                    if (r <= 0) return r;
+                    done = done && b.bitplane == 0;
+                }
+                if (!state) {                                       // plane 0 alone
+                    if (++o >= (size_t)kBands) {
+                        ++level;
+                        o = level < levels;
+                        if (o == 0u) { level = 0; state = plane = planes > 1u; if (!state) break; }
+                    }
+                } else if (++plane >= planes) {                     // planes 1.. per orientation
+                    plane = 1;
+                    if (++o >= (size_t)kBands) {
+                        ++level;
+                        o = level < levels;
+                        if (o == 0u) { level = 0; state = plane = 0; break; }
+                    }
+                }
+            }
+            ++round;
+        }
+        return 0;
+    }
+};
+
+struct Decoder : Coder {
+    BitReader in;
+
+    bool init_band(Band& b)                                         // SQZ_decode_init_subband :1890-1899
+    {
+        if (!init_lists(b)) return false;
         b.max_bitplane = in.bits(4);                                // -1 at the end of the buffer
         b.bitplane = b.max_bitplane;
         return true;
@@ -345,38 +390,12 @@ struct Decoder {
         b.bitplane -= b.bitplane > 0;
         return !in.at_end();
     }
-    bool run()                                                      // SQZ_schedule_task :2105-2168; false = out of memory
+    bool run()                                                      // false = out of memory
     {
-        size_t state = 0, plane = 0, level = 0, o = 0;
-        int round = 0; bool done = false;
-        while (!done && !in.at_end()) {
-            done = true;
-            for (;;) {
-                Band& b = band[plane][level][o];
-                if (round < b.round || (round > b.round && b.bitplane == 0)) done = done && round > b.round;
-                else {
-                    if (b.round == round && !init_band(b)) return false;
-                    if (!bitplane(b)) return true;
-                    done = done && b.bitplane == 0;
-                }
-                if (!state) {                                       // plane 0 alone
-                    if (++o >= (size_t)kBands) {
-                        ++level;
-                        o = level < levels;
-                        if (o == 0u) { level = 0; state = plane = planes > 1u; if (!state) break; }
-                    }
-                } else if (++plane >= planes) {                     // planes 1.. per orientation
-                    plane = 1;
-                    if (++o >= (size_t)kBands) {
-                        ++level;
-                        o = level < levels;
-                        if (o == 0u) { level = 0; state = plane = 0; break; }
-                    }
-                }
-            }
-            ++round;
-        }
-        return true;
+        return walk([&] { return in.at_end(); }, [&](Band& b, bool first) {
+            if (first && !init_band(b)) return -1;
+            return bitplane(b) ? 1 : 0;
+        }) == 0;
     }
     void round_coefficients()                                       // :2082-2103
     {
@@ -386,6 +405,114 @@ struct Decoder {
             const int16_t rm = (int16_t)(uint16_t)(((1u << b.bitplane) - 1u) ^ 1u);
             for (int32_t px = b.lsp.head; px >= 0; px = b.nodes[px].next) b.at(px) = (int16_t)(b.at(px) | rm);
         }
+    }
+};
+
+// ---- the writer: SQZ_encode behind SQZ_dwt_convert_to_sign_magnitude (:2232-2237) ----
+struct BitWriter {                                                  // SQZ_bit_buffer_t, write side :570-623
+    uint8_t *data, *ptr, *eob; uint32_t index = 0;
+    bool at_end() const { return ptr >= eob; }
+    size_t bits_used() const { return (size_t)(ptr - data) * 8u + index; }
+    bool bit(uint32_t b)
+    {
+        if (at_end()) return false;
+        *ptr |= (uint8_t)(b << (7u - index));
+        if (index < 7u) ++index; else { ++ptr; index = 0; }
+        return true;
+    }
+    bool bits(uint32_t v, uint32_t width)                           // a width of 0 still fails at the end of the buffer (:599)
+    {
+        for (;;) {
+            if (at_end()) return false;
+            const uint32_t room = 8u - index;
+            if (room >= width) {
+                *ptr |= (uint8_t)((v & ((1u << width) - 1u)) << (room - width));
+                index += width;
+                if (index > 7u) { ++ptr; index = 0; }
+                return true;
+            }
+            *ptr |= (uint8_t)((v >> (width - room)) & ((1u << room) - 1u));
+            ++ptr; index = 0; width -= room;
+        }
+    }
+};
+
+uint32_t interleave(uint32_t i)                                     // :548-556
+{
+    i &= 0x0000FFFFu; i = (i ^ (i << 8)) & 0x00FF00FFu; i = (i ^ (i << 4)) & 0x0F0F0F0Fu;
+    i = (i ^ (i << 2)) & 0x33333333u; i = (i ^ (i << 1)) & 0x55555555u;
+    return i;
+}
+
+constexpr int kUndefinedShift = -2;                                 // Encoder::init_band
+
+struct Encoder : Coder {
+    BitWriter out;
+
+    // SQZ_encode_init_subband :1866-1876.  SQZ_dwt_get_max compares SHORTS: a sign-magnitude value of 32768 or more (|coefficient| >=
+    // 16384) is a negative short and never the maximum while the band holds one value that is not.  Then max >> 1 <= 16383, max_bitplane
+    // <= 14 and everything below is defined; it is reproduced, blind to those values' top bit as the reference is.  A band of nothing but
+    // such values has a negative maximum: SQZ_ilog2 of it as uint is 32, 1u << 32 is not defined -- the image is refused.
+    int init_band(Band& b)
+    {
+        if (!init_lists(b)) return -1;
+        int16_t max = *b.data;
+        for (size_t y = 0; y < b.height; ++y) {
+            const int16_t* row = b.data + y * b.stride;
+            for (size_t x = 0; x < b.width; ++x) if (row[x] > max) max = row[x];
+        }
+        if (max < 0) return kUndefinedShift;
+        b.max_bitplane = (int)ilog2((uint32_t)(max >> 1));
+        b.bitplane = b.max_bitplane;
+        out.bits((uint32_t)b.max_bitplane, 4u);
+        return 1;
+    }
+    bool write_run(uint32_t run)                                    // SQZ_encode_write_wdr_run :1928-1939
+    {
+        const uint32_t cost = ilog2(run) - 1u;
+        if (cost <= 16u) return out.bits(interleave(run), cost * 2u);
+        return out.bits(interleave(run >> 16), (cost - 16u) * 2u) && out.bits(interleave(run), 32u);
+    }
+    bool sorting_pass(Band& b)                                      // :1953-1986
+    {
+        if (b.lip.length == 0u || b.bitplane <= 0) return true;
+        int32_t pixel = b.lip.head, prev = -1;
+        const int16_t mask = (int16_t)(uint16_t)(1u << b.bitplane);
+        uint32_t i = 1u, last = 0u;
+        while (pixel >= 0) {
+            const int16_t v = b.at(pixel);
+            if (v & mask) {
+                if (!out.bits(2u | (uint32_t)(v & 1), 1u + (last != 0u)) || !write_run(i - last)) break;
+                last = i;
+                pixel = b.exchange(b.lip, b.nsp, pixel, prev);
+            } else { prev = pixel; pixel = b.nodes[pixel].next; }
+            ++i;
+        }
+        out.bits(3u, 1u + (b.nsp.length > 0u));                     // the WDR termination: a run past the LIP
+        write_run(i - last);
+        out.bit(1u);
+        return !out.at_end();
+    }
+    bool refinement_pass(Band& b)                                   // :2022-2037
+    {
+        const int16_t mask = (int16_t)(uint16_t)(1u << b.bitplane);
+        for (int32_t pixel = b.lsp.head; pixel >= 0; pixel = b.nodes[pixel].next)
+            if (!out.bit((b.at(pixel) & mask) != 0)) break;
+        return !out.at_end();
+    }
+    bool bitplane(Band& b)                                          // SQZ_encode_bitplane :2059-2068
+    {
+        if (!sorting_pass(b) || !refinement_pass(b)) return false;
+        b.merge(b.nsp, b.lsp);
+        b.bitplane -= b.bitplane > 0;
+        return !out.at_end();
+    }
+    int run()                                                       // 0, -1 out of memory, kUndefinedShift
+    {
+        return walk([&] { return out.at_end(); }, [&](Band& b, bool first) {
+            if (first) { const int r = init_band(b); if (r < 0) return r; }
+            return bitplane(b) ? 1 : 0;
+        });
     }
 };
 
@@ -437,9 +564,61 @@ int sqz_decode_coeffs(const uint8_t* data, size_t len, int16_t* out, size_t capa
     return GAMUT_HIP_OK;
 }
 
+// SQZ_validate_input :2170-2197 with read_only = 0: too many levels are CLAMPED to what the size admits, everything else is refused
+int sqz_encode_check(gamut_hip_sqz_encode_desc* d)
+{
+    if (d->width < 8 || d->width > 65535 || d->height < 8 || d->height > 65535 || d->color_mode < 0 || d->color_mode > 3 || d->scan_order < 0 ||
+        d->scan_order > 3 || d->levels < 1 || d->levels > kMaxLevel)
+        return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz: %d x %d, colour mode %d, scan order %d, %d levels cannot be encoded (sides 8..65535, modes and scans 0..3, levels 1..8)",
+                         d->width, d->height, d->color_mode, d->scan_order, d->levels);
+    uint32_t max_level = ilog2((uint32_t)(d->width > d->height ? d->height : d->width)) - 3u;
+    if (max_level > (uint32_t)kMaxLevel) max_level = kMaxLevel;
+    if ((uint32_t)d->levels > max_level) d->levels = (int32_t)max_level;
+    return GAMUT_HIP_OK;
+}
+
+// SQZ_encode :2216-2237 without the colour stage and the DWT: `d` has passed sqz_encode_check, planes is the sign-magnitude buffer
+int sqz_encode_coeffs(const int16_t* planes, const gamut_hip_sqz_encode_desc& d, uint8_t* dst, int64_t* len)
+{
+    *len = 0;
+    if (d.budget <= 6) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz: a budget of %lld bytes does not hold the 6-byte header and one more bit", (long long)d.budget);
+    std::unique_ptr<Encoder> e(new (std::nothrow) Encoder());
+    if (!e) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz: out of host memory");
+    memset(dst, 0, (size_t)d.budget);                               // saveSQZ plugins/sqz.d:167-169: the writer only ORs bits in
+    e->out = BitWriter{ dst, dst, dst + d.budget };
+    BitWriter& out = e->out;                                        // SQZ_encode_header :1901-1911
+    out.bits(0xA5u, 8u); out.bits((uint32_t)(d.width - 1), 16u); out.bits((uint32_t)(d.height - 1), 16u); out.bits((uint32_t)d.color_mode, 2u);
+    out.bits((uint32_t)(d.levels - 1), 3u); out.bits((uint32_t)d.scan_order, 2u); out.bit(d.subsampling != 0);
+    if (out.at_end()) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz: no room behind the header");      // (budget > 6: not reached)
+    e->data = const_cast<int16_t*>(planes);                         // the writer only reads them
+    e->width = (size_t)d.width; e->height = (size_t)d.height; e->levels = (size_t)d.levels; e->planes = d.color_mode == 0 ? 1 : 3;
+    e->mode = d.color_mode; e->scan = d.scan_order; e->subsampling = d.subsampling != 0;
+    e->layout();
+    const int r = e->run();
+    if (r == kUndefinedShift)
+        return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz: a subband holds nothing but coefficients of magnitude 16384 and more; the reference's bit plane for it is 1u << 32");
+    if (r < 0) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz: out of host memory for a subband's lists");
+    *len = (int64_t)((out.bits_used() + 7u) / 8u);
+    return GAMUT_HIP_OK;
+}
+
 // The two sRGB tables of the colour stage (SQZ_sRGB_to_linear :1251-1285, SQZ_linear_to_sRGB :1287-1321) are the sRGB transfer
 // functions sampled at i / 255 and i / 511, rounded to nearest: the formulas reproduce every entry (tests/test_sqz_cpu.py pins the
-// SHA-256 of both).  Only the second is needed to decode.
+// SHA-256 of both).  The second decodes, the first encodes.
+const uint16_t* sqz_srgb_to_linear_table()
+{
+    static uint16_t t[256];
+    static const bool once = [] {
+        for (int i = 0; i < 256; ++i) {
+            double v = i / 255.0;
+            v = v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4);
+            t[i] = (uint16_t)floor(65535.0 * v + 0.5);
+        }
+        return true;
+    }();
+    (void)once;
+    return t;
+}
 const uint8_t* sqz_linear_to_srgb_table()
 {
     static uint8_t t[512];
@@ -481,5 +660,27 @@ int gamut_hip_sqz_decode_coeffs(const uint8_t* data, size_t len, int16_t* planes
 }
 
 const uint8_t* gamut_hip_sqz_linear_to_srgb_table(void) { return sqz_linear_to_srgb_table(); }
+
+int64_t gamut_hip_sqz_budget_from_flags(int width, int height, int flags)                  // saveSQZ plugins/sqz.d:153-158
+{
+    int bpp8 = (flags >> 5) & 0xff;
+    if (bpp8 == 0) bpp8 = 0x50;
+    const double bpp = (double)((float)bpp8 / 32.0f);
+    return 6 + (int64_t)((double)width * height * bpp / 8.0);
+}
+
+int gamut_hip_sqz_encode_coeffs(const int16_t* planes, const gamut_hip_sqz_encode_desc* desc, uint8_t* dst, int64_t* len)
+{
+    clear_error();
+    if (len) *len = 0;
+    if (!planes || !desc || !dst || !len) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz_encode_coeffs: NULL argument");
+    gamut_hip_sqz_encode_desc d = *desc;
+    if (int rc = sqz_encode_check(&d)) return rc;
+    try {
+        return sqz_encode_coeffs(planes, d, dst, len);
+    } catch (...) {
+        return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_encode_coeffs: out of host memory");
+    }
+}
 
 } // extern "C"

@@ -37,6 +37,7 @@ IMAGE_SIGNATURES = {
     "gamut_image_save_tga_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_tga_to_file": (_i, [_vp, C.c_char_p, _i]),
     "gamut_image_save_qoix_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_qoix_to_file": (_i, [_vp, C.c_char_p, _i]),
     "gamut_image_save_dds_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_dds_to_file": (_i, [_vp, C.c_char_p, _i]),
+    "gamut_image_save_sqz_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_sqz_to_file": (_i, [_vp, C.c_char_p, _i]),
 }
 _bound = False
 
@@ -60,7 +61,12 @@ FORMAT_QOIX = 3                                                # ImageFormat.QOI
 FORMAT_DDS = 4                                                 # ImageFormat.DDS: written only (save_dds_to_memory), as in the reference; save_to_memory(4) returns None
 FORMAT_GIF = 6                                                 # ImageFormat.GIF: every frame a layer, read and written (rgba8)
 FORMAT_TGA = 5                                                 # ImageFormat.TGA: read (loadFromMemory) and written (save_tga_to_memory); save_to_memory(5) returns None
-FORMAT_SQZ = 9                                                 # ImageFormat.SQZ: read only (loadFromMemory): l8 / rgb8; save_to_memory(9) returns None
+FORMAT_SQZ = 9                                                 # ImageFormat.SQZ: read (loadFromMemory: l8 / rgb8) and written (save_sqz_to_memory: rgb8); save_to_memory(9) returns None
+ENCODE_SQZ_QUALITY_DEFAULT = 0                                 # types.d:251-264: the byte budget in bits per pixel * 32, shifted left by 5; 0 means 2.5 bpp
+(ENCODE_SQZ_QUALITY_BPP1_0, ENCODE_SQZ_QUALITY_BPP1_25, ENCODE_SQZ_QUALITY_BPP1_5, ENCODE_SQZ_QUALITY_BPP1_75, ENCODE_SQZ_QUALITY_BPP2_0,
+ ENCODE_SQZ_QUALITY_BPP2_25, ENCODE_SQZ_QUALITY_BPP2_5, ENCODE_SQZ_QUALITY_BPP2_75, ENCODE_SQZ_QUALITY_BPP3_0, ENCODE_SQZ_QUALITY_BPP3_25,
+ ENCODE_SQZ_QUALITY_BPP3_5, ENCODE_SQZ_QUALITY_BPP3_75) = (v << 5 for v in range(0x20, 0x80, 8))
+ENCODE_SQZ_QUALITY_MAX = 0xff << 5
 FORMAT_BMP = 7                                                 # ImageFormat.BMP (types.d:14-28)
 ENCODE_PNG_COMPRESSION_DEFAULT, ENCODE_PNG_COMPRESSION_FAST, ENCODE_PNG_COMPRESSION_SMALL = 0, 2, 10                # types.d:220-248
 (ENCODE_PNG_COMPRESSION_0, ENCODE_PNG_COMPRESSION_1, ENCODE_PNG_COMPRESSION_2, ENCODE_PNG_COMPRESSION_3, ENCODE_PNG_COMPRESSION_4,
@@ -263,6 +269,21 @@ class Image:
     saveDDSToMemory = save_dds_to_memory
 
     def saveDDSToFile(self, path, flags=0): return bool(self.L.gamut_image_save_dds_to_file(self.h, str(path).encode(), flags))
+
+    # saveSQZ (plugins/sqz.d:141-201): rgb8 with sides of at least 8, layer 0; Oklab, 7 levels, snake scan; flags = ENCODE_SQZ_QUALITY_*
+    def save_sqz_to_memory(self, flags=0):
+        """the SQZ file as bytes (the bytes used, at most the budget the flags give), or None when the image is refused"""
+        n = _sz(0)
+        p = self.L.gamut_image_save_sqz_to_memory(self.h, flags, C.byref(n))
+        if not p:
+            return None
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            self.L.gamut_free_encoded_image(p)
+    saveSQZToMemory = save_sqz_to_memory
+
+    def saveSQZToFile(self, path, flags=0): return bool(self.L.gamut_image_save_sqz_to_file(self.h, str(path).encode(), flags))
 
     @property
     def isDevice(self): return bool(self.L.gamut_image_is_device(self.h))

@@ -608,7 +608,7 @@ float   gamut_hip_tga_last_encode_stage_ms(int stage);
  * bit stream -- WDR bit planes over linked lists per subband, interleaved by a schedule -- and leaves the reference's coefficient
  * buffer as it stands after SQZ_decode_round_coefficients.  The BACK END (HIP kernels, gamut_hip_sqz_reconstruct_batch_device) is
  * SQZ_dwt_convert_from_sign_magnitude, SQZ_idwt (up to eight levels of the in-place 5/3 integer IDWT per plane) and one of the four
- * inverse colour transforms (grey, YCoCg-R, integer Oklab, LOG-L1), bit for bit.  Encoding (saveSQZ) is not provided.
+ * inverse colour transforms (grey, YCoCg-R, integer Oklab, LOG-L1), bit for bit.  Encoding (saveSQZ) is the next section.
  * Refusals the reference does not have: an allocation that cannot be had (GAMUT_HIP_ERR_OUT_OF_MEMORY).  Nothing else deviates.
  * (Declared typedef-first: the layout of both structs is pinned by tests/c/sqz_abi_layout.c and tests/test_sqz_cpu.py.) */
 typedef struct gamut_hip_sqz_info gamut_hip_sqz_info;
@@ -658,6 +658,68 @@ const uint8_t* gamut_hip_sqz_linear_to_srgb_table(void);
  * last call -- 0: the back end's kernels (GPU time), 1: the host front end of the file-level call (wall clock), 2: staging copy and
  * upload (wall clock until the upload is queued); -1 when timing is off, nothing was decoded or `stage` is out of range */
 float gamut_hip_sqz_last_decode_stage_ms(int stage);
+
+/* ---- SQZ encode (SQZ_encode, codecs/sqz.d:2208-2240; saveSQZ, plugins/sqz.d:141-201) -----------------------------------------------
+ * The decoder's split, mirrored.  The FRONT HALF (HIP kernels, gamut_hip_sqz_analyze_batch_device) is SQZ_color_process(read = 1) for
+ * the four colour modes, SQZ_dwt (the in-place 5/3 integer DWT, one launch per level over the whole batch) and
+ * SQZ_dwt_convert_to_sign_magnitude, bit for bit -- the horizontal pass's untruncated running ints and every 16-bit wrap included --
+ * and ends with the reference's coefficient buffer in device memory, exactly what gamut_hip_sqz_reconstruct_batch_device consumes.
+ * The BACK HALF (host threads, gamut_hip_sqz_encode_coeffs) is SQZ_encode_header and SQZ_schedule_task over SQZ_encode_init_subband /
+ * SQZ_encode_bitplane: the embedded bit-plane writer, cut at the byte budget.
+ * Deviations: (1) a subband in which EVERY sign-magnitude value is a negative short (every |coefficient| >= 16384) is refused with
+ * GAMUT_HIP_ERR_INVALID_ARG: the reference takes the maximum as a signed short, gets bit plane 32 from it and shifts 1u by 32, which
+ * is not defined.  A band with at least one smaller value is written as the reference writes it (the large values' top bit is not
+ * seen).  8-bit pixels cannot produce either.  (2) An allocation that cannot be had is GAMUT_HIP_ERR_OUT_OF_MEMORY.
+ * (Declared typedef-first: the layout is pinned by tests/c/sqz_encode_abi_layout.c and tests/test_sqz_encode_cpu.py.) */
+typedef struct gamut_hip_sqz_encode_desc gamut_hip_sqz_encode_desc;
+struct gamut_hip_sqz_encode_desc {
+    int32_t width, height;          /* 8..65535 each */
+    int32_t color_mode;             /* 0 grey (l8 pixels, one plane), 1 YCoCg-R, 2 Oklab, 3 LOG-L1 (rgb8 pixels, three planes) */
+    int32_t levels;                 /* 1..8; more than ilog2(min side) - 3 is CLAMPED to that, as SQZ_validate_input(read_only = 0) does */
+    int32_t scan_order;             /* 0 raster, 1 snake, 2 Morton, 3 Hilbert */
+    int32_t subsampling;            /* 0 / not 0: chroma planes scheduled one round later */
+    int64_t budget;                 /* bytes the file may take, header included; the analysis entries do not look at it */
+};
+/* saveSQZ's budget, to the letter: bpp8 = (flags >> 5) & 0xff, 0 meaning 0x50; bpp = bpp8 / 32.0f widened to double;
+ * 6 + (int64)((double)width * height * bpp / 8.0) */
+int64_t gamut_hip_sqz_budget_from_flags(int width, int height, int flags);
+/* the front half: `count` images resident in device memory, l8 (colour mode 0) or rgb8, rows src_pitch[i] bytes apart (padded or
+ * negative, any byte alignment; exactly width * planes bytes of a row are read) -> planes * width * height int16 coefficients per
+ * image at coeffs + coeff_offset[i] (device, counted in int16 elements, >= 0): sign-magnitude with bit 0 the sign, planes one after
+ * another, subbands interleaved in place (SQZ_common_init_context).  src, src_pitch, descs, coeff_offset and status_host are host
+ * arrays; status_host may be NULL.  An image whose desc is refused (a side outside 8..65535, a mode or scan order outside 0..3,
+ * levels outside 1..8, a NULL src[i], a negative offset) gets GAMUT_HIP_ERR_INVALID_ARG and writes nothing, the others are done, and
+ * the call returns the status of the lowest-numbered refused image ("image %d: ...").  One launch per DWT level, shallowest first --
+ * at most eight whatever the number of images; the first does the colour transform in its load, every one converts to
+ * sign-magnitude in its stores.  Nothing outside an image's own coefficients is written.  Returns when they are in place. */
+int gamut_hip_sqz_analyze_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_sqz_encode_desc* descs, int count,
+                                       int16_t* coeffs, const int64_t* coeff_offset, int* status_host, void* stream);
+/* the same level kernels fed with two's-complement int16 planes in raster order, planes one after another, at planes_in +
+ * coeff_offset[i] (device; must not overlap `coeffs`): SQZ_dwt and SQZ_dwt_convert_to_sign_magnitude alone, the exact inverse of
+ * what gamut_hip_sqz_reconstruct_batch_device does before its colour stage.  color_mode only gives the plane count.  This is the
+ * way to values no 8-bit pixel produces. */
+int gamut_hip_sqz_dwt_batch_device(const int16_t* planes_in, const gamut_hip_sqz_encode_desc* descs, int count, int16_t* coeffs,
+                                   const int64_t* coeff_offset, int* status_host, void* stream);
+/* the back half (host, no GPU needed), the mirror of gamut_hip_sqz_decode_coeffs: header and bit planes of the coefficient buffer
+ * `planes` (as the front half leaves it) into dst[0 .. desc->budget), which is cleared first as saveSQZ clears it; *len = (bits used
+ * + 7) / 8.  levels is clamped as above.  A budget of at most 6 bytes is GAMUT_HIP_ERR_INVALID_ARG before anything is written (the
+ * reference's SQZ_BUFFER_TOO_SMALL: the header's verdict is !eob after its last bit).  On a refusal *len is 0 and dst[0 .. budget)
+ * is unspecified. */
+int gamut_hip_sqz_encode_coeffs(const int16_t* planes, const gamut_hip_sqz_encode_desc* desc, uint8_t* dst, int64_t* len);
+/* device pixels -> files: the front half, ONE download of the batch's coefficients into pinned staging, the back half on the
+ * library's host worker pool (one image per thread, at most 16 threads).  `out` is HOST memory -- this is the one encoder whose files
+ * land on the host: the writer runs there, and nobody asked for the files in device memory.  File i goes to out + out_offset[i],
+ * where descs[i].budget bytes must be writable; out_len[i] (host) is its length, 0 for a refused image.  Nothing outside
+ * [out_offset[i], out_offset[i] + out_len[i]) is written.  Refusals and the returned status as for the front half; a budget of at
+ * most 6 bytes and deviation (1) are refusals too. */
+int gamut_hip_sqz_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_sqz_encode_desc* descs, int count,
+                                      const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host, void* stream);
+/* the host drop-in for SQZ_encode: pixels in host memory (rows `pitch` bytes apart, may be negative) go up through pinned staging,
+ * the call above follows; the file comes back in malloc memory (*out_len bytes, free()), or NULL with the thread's message */
+void* gamut_hip_sqz_write_to_mem(const void* data, int pitch, const gamut_hip_sqz_encode_desc* desc, int* out_len);
+/* measurements, under the decoder's GAMUT_HIP_SQZ_TIMING=1: milliseconds of the calling thread's last call -- 0: the front half's
+ * kernels (GPU time), 1: the host writer (wall clock), 2: download and staging (wall clock); -1 otherwise */
+float gamut_hip_sqz_last_encode_stage_ms(int stage);
 
 /* ---- DDS / BC7 encode (saveDDS, plugins/dds.d:47-216; bc7enc16_compress_block, codecs/bc7enc16.d) --------------------------------
  * The file saveDDS writes, byte for byte: "DDS ", DDSURFACEDESC2, DDS_HEADER_DXT10 (148 bytes, DXGI_FORMAT_BC7_UNORM), then one

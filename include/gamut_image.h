@@ -171,6 +171,22 @@ int      gamut_image_save_qoix_to_file(gamut_image* img, const char* path, int f
  * identified or loaded, as in the reference.  The image's state and error are left as they were.  Freed with gamut_free_encoded_image. */
 uint8_t* gamut_image_save_dds_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
 int      gamut_image_save_dds_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
+/* saveSQZ (plugins/sqz.d:141-201; gamut_hip_sqz_encode*): rgb8 only, both sides at least 8, layer 0 of a layered image; Oklab, 7
+ * levels (clamped to what the size admits), chroma scheduled one round later, snake scan.  The flags carry the byte budget
+ * (GAMUT_ENCODE_SQZ_QUALITY_*, gamut_hip_sqz_budget_from_flags); the file is the bytes the stream used, which is less than the budget
+ * when the image is lossless below it.  GAMUT_FORMAT_SQZ (9) is not dispatched from the two generic entries above (they return
+ * NULL / 0 for it).  Host-resident and device-resident images; the image's state and error are left as they were.  Freed with
+ * gamut_free_encoded_image. */
+enum {
+    GAMUT_ENCODE_SQZ_QUALITY_DEFAULT = 0,          /* 2.5 bits per pixel */
+    GAMUT_ENCODE_SQZ_QUALITY_BPP1_0 = 0x20 << 5, GAMUT_ENCODE_SQZ_QUALITY_BPP1_25 = 0x28 << 5, GAMUT_ENCODE_SQZ_QUALITY_BPP1_5 = 0x30 << 5,
+    GAMUT_ENCODE_SQZ_QUALITY_BPP1_75 = 0x38 << 5, GAMUT_ENCODE_SQZ_QUALITY_BPP2_0 = 0x40 << 5, GAMUT_ENCODE_SQZ_QUALITY_BPP2_25 = 0x48 << 5,
+    GAMUT_ENCODE_SQZ_QUALITY_BPP2_5 = 0x50 << 5, GAMUT_ENCODE_SQZ_QUALITY_BPP2_75 = 0x58 << 5, GAMUT_ENCODE_SQZ_QUALITY_BPP3_0 = 0x60 << 5,
+    GAMUT_ENCODE_SQZ_QUALITY_BPP3_25 = 0x68 << 5, GAMUT_ENCODE_SQZ_QUALITY_BPP3_5 = 0x70 << 5, GAMUT_ENCODE_SQZ_QUALITY_BPP3_75 = 0x78 << 5,
+    GAMUT_ENCODE_SQZ_QUALITY_MAX = 0xff << 5       /* about 8 bits per pixel */
+};
+uint8_t* gamut_image_save_sqz_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
+int      gamut_image_save_sqz_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
 
 #ifdef __cplusplus
 }
