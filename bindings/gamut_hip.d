@@ -222,6 +222,17 @@ extern(C)
                                             const(long)* out_offset, ubyte* out_, long* out_len, int* status_host, void* stream);
     void* gamut_hip_sqz_write_to_mem(const(void)* data, int pitch, const(gamut_hip_sqz_encode_desc)* desc, int* out_len);
     float gamut_hip_sqz_last_encode_stage_ms(int stage);
+    // SQZ write on the device: the bit-plane writer as HIP kernels.  write_batch_device takes coefficient buffers in DEVICE memory (as
+    // analyze_batch_device leaves them) and leaves the files in DEVICE memory; encode_batch_to_device is the front half followed by it.
+    // set_writer(0 host / 1 device) chooses what encode_batch_device, write_to_mem and the Image layer run; it returns the previous value.
+    int   gamut_hip_sqz_write_batch_device(const(short)* coeffs, const(long)* coeff_offset, const(gamut_hip_sqz_encode_desc)* descs, int count,
+                                           const(long)* out_offset, ubyte* out_, long* out_len, int* status_host, void* stream);
+    int   gamut_hip_sqz_encode_batch_to_device(const(ubyte*)* src, const(long)* src_pitch, const(gamut_hip_sqz_encode_desc)* descs, int count,
+                                               const(long)* out_offset, ubyte* out_, long* out_len, int* status_host, void* stream);
+    int   gamut_hip_sqz_scan_order(int order, int width, int height, ushort* xy);
+    int   gamut_hip_sqz_write_chunk();
+    float gamut_hip_sqz_last_write_stage_ms(int stage);
+    int   gamut_hip_sqz_set_writer(int which);
     // TGA encode: TGAEncoder as saveTGA drives it (codecs/tga.d:57-281, plugins/tga.d:128-150), byte for byte; comp is the source's
     // channel count (1 l8, 2 la8, 3 rgb8, 4 rgba8).  Deviations: width or height 0 and a bound above int.max are refused.
     long  gamut_hip_tga_encode_bound(int width, int height, int comp);

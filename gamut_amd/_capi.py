@@ -200,6 +200,13 @@ SIGNATURES = {
                                            C.POINTER(_i64), _pi, _vp]),
     "gamut_hip_sqz_write_to_mem": (_vp, [_vp, _i, C.POINTER(SqzEncodeDesc), _pi]),
     "gamut_hip_sqz_last_encode_stage_ms": (_f, [_i]),
+    "gamut_hip_sqz_write_batch_device": (_i, [_vp, C.POINTER(_i64), C.POINTER(SqzEncodeDesc), _i, C.POINTER(_i64), _vp, C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_sqz_encode_batch_to_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(SqzEncodeDesc), _i, C.POINTER(_i64), _vp,
+                                              C.POINTER(_i64), _pi, _vp]),
+    "gamut_hip_sqz_scan_order": (_i, [_i, _i, _i, _vp]),
+    "gamut_hip_sqz_write_chunk": (_i, []),
+    "gamut_hip_sqz_last_write_stage_ms": (_f, [_i]),
+    "gamut_hip_sqz_set_writer": (_i, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

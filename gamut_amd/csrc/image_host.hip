@@ -235,6 +235,9 @@ struct gamut_image {
     // convertTo crosses PCIe twice); true = HBM (hipMalloc): loadFromMemory decodes straight into it and convertTo chains stay
     // on the device; _data / scanptr() are then device addresses (gamut_image_copy_pixels_to_host reads them back).
     bool      _device = false;
+    // Not in the reference either: the file gamut_image_save_sqz_to_device left in HBM.  Owned by the image like its device pixel
+    // storage: freed by the next such save and by gamut_image_delete.
+    uint8_t*  _deviceFile = nullptr;
 
     void error(const char* msg) { _error = msg; _type = GAMUT_PIXEL_unknown; }           // image.d:1563-1570
     void clearError() { _error = nullptr; }
@@ -605,7 +608,7 @@ int  gamut_identify_format_from_memory(const uint8_t* bytes, size_t len) { retur
 void gamut_free_image_data(void* p) { free(p); }
 
 gamut_image* gamut_image_new(void) { return new (std::nothrow) gamut_image(); }
-void gamut_image_delete(gamut_image* img) { if (img) { img->cleanupBitmapIfOwned(); delete img; } }
+void gamut_image_delete(gamut_image* img) { if (img) { img->cleanupBitmapIfOwned(); if (img->_deviceFile) (void)hipFree(img->_deviceFile); delete img; } }
 
 int gamut_image_create(gamut_image* img, int w, int h, int type, int layout) { return img->createLayered(w, h, 1, type, layout, true); }
 int gamut_image_create_layered(gamut_image* img, int w, int h, int layers, int type, int layout) { return img->createLayered(w, h, layers, type, layout, true); }
@@ -1068,7 +1071,7 @@ static uint8_t* save_sqz(gamut_image* img, int flags, size_t* len)
         if (r) *len = (size_t)n;
         return r;
     }
-    uint8_t* file = (uint8_t*)malloc((size_t)d.budget);               // the writer runs on the host: the file never is in device memory
+    uint8_t* file = (uint8_t*)malloc((size_t)d.budget);               // a host buffer for either writer (gamut_hip_sqz_set_writer): the device writer's file is downloaded into it
     if (!file) return nullptr;
     const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
     if (gamut_hip_sqz_encode_batch_device(&src, &pitch, &d, 1, &off, file, &n, &status, nullptr) != GAMUT_HIP_OK) { free(file); return nullptr; }
@@ -1082,6 +1085,25 @@ uint8_t* gamut_image_save_sqz_to_memory(gamut_image* img, int flags, size_t* len
     if (len) *len = 0;
     if (!img || !len || !img->isValid() || !img->_data) return nullptr;
     return save_sqz(img, flags, len);
+}
+// saveSQZ with the file left in HBM: device-resident rgb8 images only (a host image has no business there: save_sqz_to_memory)
+uint8_t* gamut_image_save_sqz_to_device(gamut_image* img, int flags, size_t* len)
+{
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data || !img->_device) return nullptr;
+    const int w = img->_width, h = img->_height;
+    if (w < 8 || h < 8 || w > 65535 || h > 65535 || img->_type != GAMUT_PIXEL_rgb8 || img->_layerCount < 1) return nullptr;
+    gamut_hip_sqz_encode_desc d{};
+    d.width = w; d.height = h; d.color_mode = 2; d.levels = 7; d.scan_order = 1; d.subsampling = 1;
+    d.budget = gamut_hip_sqz_budget_from_flags(w, h, flags);
+    if (img->_deviceFile) { (void)hipFree(img->_deviceFile); img->_deviceFile = nullptr; }
+    uint8_t* file = nullptr;
+    if (hipMalloc((void**)&file, (size_t)d.budget) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    if (gamut_hip_sqz_encode_batch_to_device(&src, &pitch, &d, 1, &off, file, &n, &status, nullptr) != GAMUT_HIP_OK) { (void)hipFree(file); return nullptr; }
+    img->_deviceFile = file;
+    *len = (size_t)n;
+    return file;
 }
 int gamut_image_save_sqz_to_file(gamut_image* img, const char* path, int flags)
 {

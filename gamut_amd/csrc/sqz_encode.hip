@@ -1,6 +1,7 @@
 // sqz_encode.hip -- the SQZ front half on the GPU and the calls above it: l8 / rgb8 pixels in HBM -> the reference's coefficient buffer
 // as it stands before SQZ_schedule_task, bit for bit what SQZ_color_process(read = 1), SQZ_dwt and SQZ_dwt_convert_to_sign_magnitude
-// (source/gamut/codecs/sqz.d:1153-1546, 1597-1697, 1574-1582) make of them.  The back half (the bit-plane writer) is sqz_host.hip.
+// (source/gamut/codecs/sqz.d:1153-1546, 1597-1697, 1574-1582) make of them.  The back half (the bit-plane writer) is sqz_host.hip on host
+// threads or sqz_write.hip on the device, by gamut_hip_sqz_set_writer; the files stay in HBM only with the latter.
 //
 // THE REFERENCE'S ORDER, AND WHY A LEVEL IS DATA-PARALLEL.  SQZ_dwt_5_3i (:1645-1673) starts with nnn = row 3, nn = row 2 (SQZ_mirror of
 // -3 and -2) and walks i = -2, 0, 2, ..: n = row i + 1, r = row i + 2 (mirrored); the horizontal passes of n (if nn <= r) and of r (if
@@ -39,11 +40,10 @@
 // one unit per tile for ALL planes: the colour transform sits in its load and is done once per pixel and tile.
 #include "common.hpp"
 #include "encode_host.hpp"
+#include "sqz_write.hpp"
 
 namespace gamut {
-int  sqz_encode_check(gamut_hip_sqz_encode_desc* d);                                             // sqz_host.hip
-int  sqz_encode_coeffs(const int16_t* planes, const gamut_hip_sqz_encode_desc& d, uint8_t* dst, int64_t* len);
-const uint16_t* sqz_srgb_to_linear_table();
+const uint16_t* sqz_srgb_to_linear_table();                                                      // sqz_host.hip
 namespace {
 
 constexpr int kThreads = 256, kTW = 128, kTH = 16, kRows = kTH + 3, kCols = kTW + 3, kHalf = kTW / 2;
@@ -286,17 +286,14 @@ int forward(const std::vector<Source>& src, const gamut_hip_sqz_encode_desc* des
     return GAMUT_HIP_OK;
 }
 
-// The lowest-numbered refused image of a batch call, with the message it was refused with
-struct Refusals {
-    int first_bad = -1, first_rc = GAMUT_HIP_OK; char first_msg[200] = { 0 };
-    int* status;
-    void refuse(int i, int rc)
-    {
-        if (status) status[i] = rc;
-        if (first_bad < 0 || i < first_bad) { first_bad = i; first_rc = rc; snprintf(first_msg, sizeof(first_msg), "%s", last_error_buf()); }
-    }
-    int verdict() const { return first_bad >= 0 ? set_error(first_rc, "image %d: %s", first_bad, first_msg) : (int)GAMUT_HIP_OK; }
-};
+using Refusals = SqzRefusals;                                       // sqz_write.hpp
+
+// Which back half the file-level calls run: 0 the host writer (sqz_host.hip), 1 the device writer (sqz_write.hip)
+std::atomic<int>& writer_switch()
+{
+    static std::atomic<int> w{ [] { const char* e = getenv("GAMUT_HIP_SQZ_WRITER"); return e && !strcmp(e, "device") ? 1 : 0; }() };
+    return w;
+}
 
 int analyze_batch(const uint8_t* const* src, const int64_t* src_pitch, const int16_t* planes_in, const gamut_hip_sqz_encode_desc* descs, int count,
                   int16_t* coeffs, const int64_t* coeff_offset, int* status_host, hipStream_t stream)
@@ -318,9 +315,11 @@ int analyze_batch(const uint8_t* const* src, const int64_t* src_pitch, const int
     return bad.verdict();
 }
 
+// out_on_device: the files stay in HBM, which only the device writer can do; a host `out` gets the writer the switch names
 int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_sqz_encode_desc* descs, int count, const int64_t* out_offset,
-                 uint8_t* out, int64_t* out_len, int* status_host, hipStream_t stream)
+                 uint8_t* out, int64_t* out_len, int* status_host, hipStream_t stream, bool out_on_device = false)
 {
+    const bool device_writer = out_on_device || writer_switch().load(std::memory_order_relaxed) == 1;
     static const bool timing = env_flag("GAMUT_HIP_SQZ_TIMING");
     std::vector<gamut_hip_sqz_encode_desc> checked(descs, descs + count);
     std::vector<Source> sources((size_t)count);
@@ -348,9 +347,17 @@ int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamu
         static thread_local PerDevice<DeviceScratch> coeff_pd;
         static thread_local PerDevice<PinnedScratch> stage_pd;
         int16_t* dco = (int16_t*)coeff_pd.cur().get(bytes, stream);
-        int16_t* hco = (int16_t*)stage_pd.cur().get(bytes, stream);
-        if (!dco || !hco) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_encode: staging of %zu coefficient bytes failed", bytes);
+        int16_t* hco = device_writer ? nullptr : (int16_t*)stage_pd.cur().get(bytes, stream);
+        if (!dco || (!hco && !device_writer)) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_encode: staging of %zu coefficient bytes failed", bytes);
         if (int rc = forward(sources, checked.data(), offs.data(), which, dco, stream)) return rc;
+        if (device_writer) {                                        // no coefficient leaves HBM; stages 1 and 2 do not exist (gamut_hip_sqz_last_write_stage_ms has the writer's)
+            if (timing) t_stage_ms[1] = t_stage_ms[2] = -1.0f;
+            std::vector<int> rcs;
+            if (int rc = sqz_write_files(dco, offs.data(), checked.data(), which, out_offset, out, out_on_device, out_len, rcs, stream)) return rc;
+            for (size_t k = 0; k < which.size(); ++k)
+                if (rcs[k] != GAMUT_HIP_OK) { sqz_undefined_shift_error(); bad.refuse(which[k], rcs[k]); }
+            return bad.verdict();
+        }
         const TracePoint t0 = trace_now();
         {
             StreamDrain drain;
@@ -435,6 +442,27 @@ int gamut_hip_sqz_encode_batch_device(const uint8_t* const* src, const int64_t* 
     } catch (...) {
         return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_encode_batch_device: out of host memory");
     }
+}
+
+int gamut_hip_sqz_encode_batch_to_device(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_sqz_encode_desc* descs, int count,
+                                         const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host, void* stream)
+{
+    clear_error();
+    if (count < 0 || (count > 0 && (!src || !src_pitch || !descs || !out_offset || !out || !out_len)))
+        return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz_encode_batch_to_device: bad arguments");
+    if (count == 0) return GAMUT_HIP_OK;
+    if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
+    try {
+        return encode_batch(src, src_pitch, descs, count, out_offset, out, out_len, status_host, pick_stream(stream), true);
+    } catch (...) {
+        return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_encode_batch_to_device: out of host memory");
+    }
+}
+
+int gamut_hip_sqz_set_writer(int which)
+{
+    if (which != 0 && which != 1) return writer_switch().load(std::memory_order_relaxed);
+    return writer_switch().exchange(which, std::memory_order_relaxed);
 }
 
 void* gamut_hip_sqz_write_to_mem(const void* data, int pitch, const gamut_hip_sqz_encode_desc* desc, int* out_len)

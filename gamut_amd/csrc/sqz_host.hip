@@ -23,6 +23,7 @@
 // field read as -1 at the end of the buffer is never used as an index (the reference would index SQZ_number_of_planes with it before
 // it looks at eob; the verdict is the same).
 #include "common.hpp"
+#include "sqz_write.hpp"
 #include <cmath>
 
 namespace gamut {
@@ -520,6 +521,53 @@ struct Encoder : Coder {
 
 int sqz_fail(const char* why) { return set_error(GAMUT_HIP_ERR_DECODE, "sqz: %s", why); }
 
+// Coder::layout with offsets in place of pointers, for the device writer (sqz_write.hip), which gathers the bands itself
+void sqz_band_geometry(const gamut_hip_sqz_encode_desc& d, SqzBandGeom g[kSqzSlots])
+{
+    memset(g, 0, sizeof(SqzBandGeom) * kSqzSlots);
+    const size_t planes = d.color_mode == 0 ? 1 : 3, levels = (size_t)d.levels, width = (size_t)d.width;
+    for (size_t p = 0; p < planes; ++p) {
+        size_t w = width, h = (size_t)d.height;
+        const size_t base = p * w * h;
+        for (int level = (int)levels - 1; level >= 0; --level) {
+            for (size_t o = level > 0; o < (size_t)kBands; ++o) {
+                SqzBandGeom& b = g[(p * kMaxLevel + (size_t)level) * kBands + o];
+                b.width = (uint32_t)((w + !(o & 1u)) >> 1); b.height = (uint32_t)((h + !(o > 1u)) >> 1);
+                b.round = schedule(d.color_mode, (int)p, level, (int)o) + ((d.subsampling != 0) & (int)(p > 0));
+                b.stride = (uint32_t)(width << (levels - (size_t)level));
+                size_t off = base;
+                if (o & 1u) off += (w + 1u) >> 1;
+                if (o > 1u) off += b.stride >> 1;
+                b.offset = (int64_t)off;
+            }
+            w = (w + 1u) >> 1; h = (h + 1u) >> 1;
+        }
+    }
+}
+
+// a band's LIP as init_lists fills it, as (x, y) pairs
+int sqz_scan_order(int order, int width, int height, uint16_t* xy)
+{
+    if (order < 0 || order > 3 || width < 1 || height < 1 || width > 65535 || height > 65535 || !xy)
+        return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz_scan_order: order %d, %d x %d", order, width, height);
+    const size_t w = (size_t)width, h = (size_t)height, n = w * h;
+    size_t k = 0;
+    auto put = [&](size_t x, size_t y) { if (k < n) { xy[2 * k] = (uint16_t)x; xy[2 * k + 1] = (uint16_t)y; } ++k; };      // Band::add's capacity guard
+    switch (order) {
+    case 0: for (size_t y = 0; y < h; ++y) for (size_t x = 0; x < w; ++x) put(x, y); break;
+    case 1: { Snake s(w, h, 4, 15); do put(s.x, s.y); while (s.next()); break; }
+    case 2: { Morton s(w, h); do put(s.x, s.y); while (s.next()); break; }
+    default: { Hilbert s(w, h); do put(s.x, s.y); while (s.next()); break; }
+    }
+    if (k != n) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz_scan_order: scan %d visits %zu positions of a %d x %d band", order, k, width, height);
+    return GAMUT_HIP_OK;
+}
+
+int sqz_undefined_shift_error()
+{
+    return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz: a subband holds nothing but coefficients of magnitude 16384 and more; the reference's bit plane for it is 1u << 32");
+}
+
 // SQZ_validate_input :2170-2197, read-only mode
 bool sqz_valid_geometry(int64_t w, int64_t h, int mode, int scan, int levels)
 {
@@ -595,8 +643,7 @@ int sqz_encode_coeffs(const int16_t* planes, const gamut_hip_sqz_encode_desc& d,
     e->mode = d.color_mode; e->scan = d.scan_order; e->subsampling = d.subsampling != 0;
     e->layout();
     const int r = e->run();
-    if (r == kUndefinedShift)
-        return set_error(GAMUT_HIP_ERR_INVALID_ARG, "sqz: a subband holds nothing but coefficients of magnitude 16384 and more; the reference's bit plane for it is 1u << 32");
+    if (r == kUndefinedShift) return sqz_undefined_shift_error();
     if (r < 0) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz: out of host memory for a subband's lists");
     *len = (int64_t)((out.bits_used() + 7u) / 8u);
     return GAMUT_HIP_OK;
@@ -667,6 +714,16 @@ int64_t gamut_hip_sqz_budget_from_flags(int width, int height, int flags)       
     if (bpp8 == 0) bpp8 = 0x50;
     const double bpp = (double)((float)bpp8 / 32.0f);
     return 6 + (int64_t)((double)width * height * bpp / 8.0);
+}
+
+int gamut_hip_sqz_scan_order(int order, int width, int height, uint16_t* xy)
+{
+    clear_error();
+    try {
+        return sqz_scan_order(order, width, height, xy);
+    } catch (...) {
+        return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_scan_order: out of host memory");
+    }
 }
 
 int gamut_hip_sqz_encode_coeffs(const int16_t* planes, const gamut_hip_sqz_encode_desc* desc, uint8_t* dst, int64_t* len)

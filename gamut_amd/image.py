@@ -38,6 +38,7 @@ IMAGE_SIGNATURES = {
     "gamut_image_save_qoix_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_qoix_to_file": (_i, [_vp, C.c_char_p, _i]),
     "gamut_image_save_dds_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_dds_to_file": (_i, [_vp, C.c_char_p, _i]),
     "gamut_image_save_sqz_to_memory": (_vp, [_vp, _i, C.POINTER(_sz)]), "gamut_image_save_sqz_to_file": (_i, [_vp, C.c_char_p, _i]),
+    "gamut_image_save_sqz_to_device": (_vp, [_vp, _i, C.POINTER(_sz)]),
 }
 _bound = False
 
@@ -282,6 +283,15 @@ class Image:
         finally:
             self.L.gamut_free_encoded_image(p)
     saveSQZToMemory = save_sqz_to_memory
+
+    def save_sqz_to_device(self, flags=0):
+        """the SQZ file of a device-resident rgb8 image, left in HBM: (device address, length), or None when the image is refused (a
+        host-resident one included).  The buffer belongs to the image: it stays valid until the next save_sqz_to_device on this image
+        or the image's end, and the caller never frees it."""
+        n = _sz(0)
+        p = self.L.gamut_image_save_sqz_to_device(self.h, flags, C.byref(n))
+        return (int(p), int(n.value)) if p else None
+    saveSQZToDevice = save_sqz_to_device
 
     def saveSQZToFile(self, path, flags=0): return bool(self.L.gamut_image_save_sqz_to_file(self.h, str(path).encode(), flags))
 

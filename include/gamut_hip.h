@@ -707,8 +707,9 @@ int gamut_hip_sqz_dwt_batch_device(const int16_t* planes_in, const gamut_hip_sqz
  * is unspecified. */
 int gamut_hip_sqz_encode_coeffs(const int16_t* planes, const gamut_hip_sqz_encode_desc* desc, uint8_t* dst, int64_t* len);
 /* device pixels -> files: the front half, ONE download of the batch's coefficients into pinned staging, the back half on the
- * library's host worker pool (one image per thread, at most 16 threads).  `out` is HOST memory -- this is the one encoder whose files
- * land on the host: the writer runs there, and nobody asked for the files in device memory.  File i goes to out + out_offset[i],
+ * library's host worker pool (one image per thread, at most 16 threads).  `out` is HOST memory: by default the writer runs on the
+ * host.  (With gamut_hip_sqz_set_writer(1) the device writer of the next section runs instead and only the files are downloaded;
+ * gamut_hip_sqz_encode_batch_to_device leaves them in device memory.)  File i goes to out + out_offset[i],
  * where descs[i].budget bytes must be writable; out_len[i] (host) is its length, 0 for a refused image.  Nothing outside
  * [out_offset[i], out_offset[i] + out_len[i]) is written.  Refusals and the returned status as for the front half; a budget of at
  * most 6 bytes and deviation (1) are refusals too. */
@@ -720,6 +721,40 @@ void* gamut_hip_sqz_write_to_mem(const void* data, int pitch, const gamut_hip_sq
 /* measurements, under the decoder's GAMUT_HIP_SQZ_TIMING=1: milliseconds of the calling thread's last call -- 0: the front half's
  * kernels (GPU time), 1: the host writer (wall clock), 2: download and staging (wall clock); -1 otherwise */
 float gamut_hip_sqz_last_encode_stage_ms(int stage);
+
+/* ---- SQZ write on the device (SQZ_schedule_task, codecs/sqz.d:1866-2168, as HIP kernels) ------------------------------------------
+ * The back half again, without the host: every (band, bit plane) segment of the embedded stream is a pure function of the band's
+ * coefficients in scan order, the order of the segments depends on the bands' maxima alone, and the file is the first 8 * budget
+ * bits of their concatenation -- counts, prefix sums and bit packing at computed offsets (gamut_amd/csrc/sqz_write.hip; six launches
+ * per chunk of images).  No coefficient crosses the bus: 16 bytes per image come down mid-call.  The files are byte for byte those of
+ * gamut_hip_sqz_encode_coeffs, and so are the verdicts: levels clamped, a budget of at most 6 bytes refused, deviation (1) refused
+ * exactly when the schedule reaches the band of nothing but negative shorts before the budget is spent.
+ *
+ * coeffs: DEVICE memory, image i's buffer at coeffs + coeff_offset[i] (int16 elements) as gamut_hip_sqz_analyze_batch_device leaves
+ * it; only read.  File i goes to out + out_offset[i] (DEVICE memory, any alignment), where descs[i].budget bytes must be writable;
+ * nothing outside [out_offset[i], out_offset[i] + out_len[i]) is written.  coeff_offset, descs, out_offset, out_len and status_host
+ * (may be NULL) are host arrays.  A refused image writes nothing and gets out_len 0, the others are written, and the call returns the
+ * status of the lowest-numbered refused image ("image %d: ..."); it returns when the files are in place. */
+int gamut_hip_sqz_write_batch_device(const int16_t* coeffs, const int64_t* coeff_offset, const gamut_hip_sqz_encode_desc* descs, int count,
+                                     const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host, void* stream);
+/* device pixels -> files in DEVICE memory: the front half, then the call above.  The arguments are those of
+ * gamut_hip_sqz_encode_batch_device, except that `out` is device memory. */
+int gamut_hip_sqz_encode_batch_to_device(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_sqz_encode_desc* descs, int count,
+                                         const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host, void* stream);
+/* a band's scan (host, no GPU needed): the width * height (x, y) pairs, 2 * width * height uint16, in the order SQZ_scan_init's
+ * scanner visits them -- order 0 raster, 1 snake (tile 4 x 15), 2 Morton, 3 Hilbert.  These are the tables the device writer uploads.
+ * GAMUT_HIP_ERR_INVALID_ARG for an order outside 0..3, a side below 1 or above 65535, or a NULL xy. */
+int gamut_hip_sqz_scan_order(int order, int width, int height, uint16_t* xy);
+/* the coefficients a wave of the device writer takes per step of its walk over a band (tests size their cases around it) */
+int gamut_hip_sqz_write_chunk(void);
+/* measurements, under GAMUT_HIP_SQZ_TIMING=1: milliseconds of the calling thread's last call that ran the device writer -- 0: its
+ * kernels (GPU time, all chunks), 1: building the band and scan tables (wall clock); -1 otherwise */
+float gamut_hip_sqz_last_write_stage_ms(int stage);
+/* Which writer gamut_hip_sqz_encode_batch_device, gamut_hip_sqz_write_to_mem and the Image layer's SQZ save run behind their
+ * unchanged signatures: 0 the host writer, 1 the device writer (the files alone are downloaded; gamut_hip_sqz_last_encode_stage_ms
+ * then gives -1 for stages 1 and 2).  Returns the previous value; any other argument changes nothing.  Process-wide; the initial
+ * value is GAMUT_HIP_SQZ_WRITER=host|device from the environment, default host. */
+int gamut_hip_sqz_set_writer(int which);
 
 /* ---- DDS / BC7 encode (saveDDS, plugins/dds.d:47-216; bc7enc16_compress_block, codecs/bc7enc16.d) --------------------------------
  * The file saveDDS writes, byte for byte: "DDS ", DDSURFACEDESC2, DDS_HEADER_DXT10 (148 bytes, DXGI_FORMAT_BC7_UNORM), then one

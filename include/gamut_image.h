@@ -187,6 +187,12 @@ enum {
 };
 uint8_t* gamut_image_save_sqz_to_memory(gamut_image* img, int flags, size_t* len);      /* NULL (and *len = 0) on refusal */
 int      gamut_image_save_sqz_to_file(gamut_image* img, const char* path, int flags);   /* 1 on success */
+/* The two above run the writer gamut_hip_sqz_set_writer names (GAMUT_HIP_SQZ_WRITER); the files are the same bytes either way.
+ * saveSQZ of a DEVICE-resident rgb8 image with the file left in HBM (always the device writer; no coefficient and no file byte
+ * crosses the bus): the DEVICE address of the file and *len, or NULL (and *len = 0) on refusal -- a host-resident image included.
+ * Ownership is that of the image's device pixel storage: the buffer belongs to the image, stays valid until the next
+ * gamut_image_save_sqz_to_device on this image or gamut_image_delete, and is never freed by the caller. */
+uint8_t* gamut_image_save_sqz_to_device(gamut_image* img, int flags, size_t* len);
 
 #ifdef __cplusplus
 }
