@@ -62,6 +62,12 @@ constexpr int kHostRedo = -1001;
 // where the 0x00 stuffing is dropped and the restart markers are found: GAMUT_HIP_JPEG_UNSTUFF=host / device forces either (tests, measurements)
 int unstuff_site() { const char* e = getenv("GAMUT_HIP_JPEG_UNSTUFF"); return !e || !*e ? 0 : !strcmp(e, "host") ? 1 : !strcmp(e, "device") ? 2 : 0; }
 
+// tests: GAMUT_HIP_JPEG_HOST_REDO=0 leaves a file an entropy KERNEL flagged refused (k_jpeg_entropy, k_jpeg_entropy_sync, k_jpeg_unstuff, k_prog_scan) -- the
+// host feeder behind the device pass would hide a kernel that flags a stream it should have decoded (the result is right either way, only slower).  It
+// covers the kernels' flags only: a file the HOST routes to the feeder before any kernel sees it (prepare_header: a scan header in the padding, a DC
+// category above 15; unstuff_file: a restart structure it cannot follow; the progressive preparation likewise) is decoded there as ever.
+inline bool redo_flagged_files() { const char* e = getenv("GAMUT_HIP_JPEG_HOST_REDO"); return !(e && *e && atoi(e) == 0); }
+
 void prepare_header(int i, const uint8_t* base, size_t n, gamut_hip_jpeg_frame& f, FilePrep& out, Parser& P)
 {
     P = Parser();
@@ -599,9 +605,14 @@ int collect_device_verdicts(BaselineBatch& b)
     std::vector<uint32_t> flags((size_t)count), ends((size_t)count);
     GAMUT_HIP_CHECK(hipMemcpy(flags.data(), b.st, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
     GAMUT_HIP_CHECK(hipMemcpy(ends.data(), b.d_scan_end, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const bool redo_flagged = redo_flagged_files();
     for (int i = 0; i < count; ++i) {
         FilePrep& fp = b.prep[(size_t)i];
         if (fp.rc != GAMUT_HIP_OK) continue;
+        if (flags[(size_t)i] && !redo_flagged) {
+            fp.rc = GAMUT_HIP_ERR_DECODE; snprintf(fp.msg, sizeof(fp.msg), "image %d: jpeg: the entropy kernels flagged the scan (status %u), and the host feeder is switched off", i, flags[(size_t)i]);
+            continue;
+        }
         if (flags[(size_t)i]) { fp.rc = kHostRedo; continue; }
         const size_t n = b.len[i];
         const size_t e = fp.dev_unstuff ? (ends[(size_t)i] == 0xFFFFFFFFu ? n : fp.scan_pos + ends[(size_t)i]) : fp.scan_end;

@@ -17,6 +17,7 @@ const uint8_t kZag[64] = { 0,1,8,16,9,2,3,10,17,24,32,25,18,11,4,5,12,19,26,33,4
 struct HuffTable {
     bool    defined = false;
     bool    oversubscribed = false;  // the lengths claim more than the code space: make_huff_table writes behind look_up[] / aliases tree nodes -- no table to match
+    bool    tree_overflow = false;   // the code words of 9 bits and more need more than the 512 slots of make_huff_table's bit tree (:2851-2987): it writes behind the array
     uint8_t bits[17] = {};        // number of codes per length
     uint8_t vals[256] = {};
     // fast path: 10-bit window -> (code length << 8) | symbol, 0 when the code is longer (or the window begins no code word)
@@ -31,7 +32,7 @@ struct HuffTable {
     bool build()                   // false: the code-length counts over-subscribe the code space (not a prefix code)
     {
         int code = 0, k = 0;
-        span = 0; oversubscribed = false;
+        span = 0; oversubscribed = false; tree_overflow = false;
         for (int len = 1; len <= 16; ++len) span += (uint32_t)bits[len] << (16 - len);
         memset(size_of, 0, sizeof(size_of)); dc_limit = 0; twice = false;
         for (int len = 1; len <= 16; ++len) for (int i = 0; i < bits[len]; ++i, ++k) {
@@ -57,6 +58,18 @@ struct HuffTable {
             }
             code <<= 1;
         }
+        // make_huff_table gives every prefix of 8 bits and more that longer code words share a pair of tree slots (nextfreeentry -= 2), 512 slots in
+        // all and no check: a legal code of many long words -- 2, 4, .. 64 words of 10 .. 15 bits and 129 of 16 need 258 pairs -- runs over the end.
+        // (The code words stand in numerical order, so the words under one prefix are neighbours.)
+        int pairs = 0;
+        for (int pre = 8; pre <= 15; ++pre) {
+            int32_t last = -1; code = 0;
+            for (int len = 1; len <= 16; ++len) {
+                for (int i = 0; i < bits[len]; ++i, ++code) if (len > pre && (code >> (len - pre)) != last) { last = code >> (len - pre); ++pairs; }
+                code <<= 1;
+            }
+        }
+        tree_overflow = pairs > 256;
         return true;
     }
     // bits taken by a window no code word covers (w >= span); `two_arg`: the progressive variant of huff_decode
@@ -423,6 +436,7 @@ bool scan_tables_ok(const Parser& P, gamut_hip_jpeg_frame* f)
         if (sc.se > 0 && (P.ta[c] >= 8 || !P.huff[P.ta[c]].defined)) { fail(f, P.ta[c] >= 8 ? "bad Huffman table selector" : "undefined Huffman table"); return false; }
     }
     for (int t = 0; t < 8; ++t) if (P.huff[t].defined && P.huff[t].oversubscribed) { fail(f, "bad DHT counts (not a prefix code)"); return false; }
+    for (int t = 0; t < 8; ++t) if (P.huff[t].defined && P.huff[t].tree_overflow) { fail(f, "a Huffman table of more long code words than the reference's bit tree holds"); return false; }
     for (int i = 0; i < sc.ncomp; ++i) if (!P.quant_def[P.tq[sc.comp[i]]]) { fail(f, "undefined quant table"); return false; }
     return true;
 }

@@ -1052,9 +1052,13 @@ int progressive_decode_device(const uint8_t* const* data, const size_t* len, con
                 for (int i : idx) { lo = std::min(lo, i); hi = std::max(hi, i); }
                 std::vector<uint32_t> flags((size_t)(hi - lo + 1));
                 GAMUT_HIP_CHECK(hipMemcpy(flags.data(), st + lo, flags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                const bool redo_flagged = redo_flagged_files();     // (tests: off = what k_prog_scan flagged stays refused)
                 for (int k = 0; k < n; ++k) {
                     ProgPrep& pp = prep[(size_t)k];
-                    if (pp.rc == GAMUT_HIP_OK && flags[(size_t)(idx[(size_t)k] - lo)]) pp.rc = kHostRedo;
+                    const uint32_t fl = flags[(size_t)(idx[(size_t)k] - lo)];
+                    if (pp.rc != GAMUT_HIP_OK || !fl) continue;
+                    if (redo_flagged) pp.rc = kHostRedo;
+                    else { pp.rc = GAMUT_HIP_ERR_DECODE; snprintf(pp.msg, sizeof(pp.msg), "image %d: jpeg: the progressive scan kernel flagged the file (status %u), and the host feeder is switched off", idx[(size_t)k], fl); }
                 }
             }
             ms_kernels = ms_since(t_k);

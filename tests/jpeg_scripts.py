@@ -131,8 +131,27 @@ def _scan_symbols(blocks_of, comps, ss, se, ah, al, units, restart):
     return segs
 
 
-def progressive_with_script(baseline, script, restart=0):
-    """baseline: bytes of a baseline JPEG (any sampling mode the oracle's feeder takes).  -> bytes of a progressive file with the given scans."""
+def comb_lengths(n):
+    """code lengths for n symbols that run through the lengths 1 .. 16 instead of giving every symbol 8 bits: up to 16 symbols get lengths spread
+    from 1 to 16, one code each (17: a second 16-bit code); more than that one code of every length from `first` to 16 and the rest at 8 bits,
+    `first` the smallest the code space allows.  Ascending, as a DHT lists them."""
+    if n == 1:
+        return [1]
+    if n <= 16:
+        return [1 + (i * 15) // (n - 1) for i in range(n)]
+    if n == 17:
+        return list(range(1, 17)) + [16]
+    for first in range(2, 8):
+        lens = sorted([ln for ln in range(first, 17) if ln != 8] + [8] * (n - len([ln for ln in range(first, 17) if ln != 8])))
+        if sum(1 << (16 - ln) for ln in lens) <= 1 << 16:
+            return lens
+    raise ValueError("too many symbols for a comb")
+
+
+def progressive_with_script(baseline, script, restart=0, tables="flat"):
+    """baseline: bytes of a baseline JPEG (any sampling mode the oracle's feeder takes).  -> bytes of a progressive file with the given scans.
+    tables: "flat" -- every symbol of a scan an 8-bit code; "comb" -- code lengths 1 .. 16 (comb_lengths): long codes in every scan."""
+    assert tables in ("flat", "comb")
     d = O.DecodedJpeg(baseline)
     hdr = _segments(baseline)
     qt = {}
@@ -185,8 +204,13 @@ def progressive_with_script(baseline, script, restart=0):
         if not dc_refine:
             syms = sorted({e[1] for sg in segs for e in sg if e[0] == "s"}) or [0]
             assert len(syms) <= 255
-            code = {s: i for i, s in enumerate(syms)}                          # every symbol an 8-bit code, in order: canonical
-            counts = [0] * 16; counts[7] = len(syms)
+            lens = [8] * len(syms) if tables == "flat" else comb_lengths(len(syms))     # every symbol an 8-bit code, or the comb; in order: canonical
+            counts = [0] * 16
+            code, nxt = {}, 0
+            for k, (sym, ln) in enumerate(zip(syms, lens)):
+                nxt <<= ln - (lens[k - 1] if k else ln)
+                code[sym] = (nxt, ln); nxt += 1
+                counts[ln - 1] += 1
             out += b"\xff\xc4" + (2 + 1 + 16 + len(syms)).to_bytes(2, "big") + bytes([(0x10 if ss else 0x00)]) + bytes(counts) + bytes(syms)
         out += b"\xff\xda" + (6 + 2 * len(comps)).to_bytes(2, "big") + bytes([len(comps)])
         for c in comps:
@@ -198,7 +222,7 @@ def progressive_with_script(baseline, script, restart=0):
             bw = _Bits()
             for e in sg:
                 if e[0] == "s":
-                    bw.put(code[e[1]], 8)
+                    bw.put(*code[e[1]])
                 else:
                     bw.put(e[1], e[2])
             bw.flush()

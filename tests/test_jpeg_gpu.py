@@ -472,20 +472,26 @@ def test_device_progressive_decode(hip, progressive_mode):
         assert np.array_equal(zz, d.max_zag), k
 
 
-def _scripted_files():
+def _scripted_files(tables="flat"):
     """progressive files with scan scripts libjpeg never writes (tests/jpeg_scripts.py): bands cut four ways under one refinement scan, DC scans
-    per component under an interleaved refinement, spectral selection only, three bit planes -- with and without restart intervals"""
+    per component under an interleaved refinement, spectral selection only, three bit planes -- with and without restart intervals.
+    tables="comb": the two smaller images under DEEP and FOUR_BANDS, code lengths 1 .. 16 in every table (jpeg_scripts.comb_lengths)
+    instead of 8-bit codes throughout -- k_prog_scan's second level and canonical search, which the flat tables never reach"""
     import io
     from PIL import Image
     import gen
     import jpeg_scripts as J
+    comb = tables == "comb"
     blobs = []
     for (w, h, kw) in ((203, 117, dict(quality=90, subsampling=2)), (131, 97, dict(quality=75, subsampling=0)), (200, 120, dict(quality=95, subsampling=1)),
-                       (640, 360, dict(quality=85, subsampling=2))):
+                       (640, 360, dict(quality=85, subsampling=2)))[:2 if comb else 4]:
         bio = io.BytesIO(); Image.fromarray(gen.synth_rgb(w, h, 31)).save(bio, "JPEG", **kw)
-        for name, sc in J.SCRIPTS.items():
+        for sc in ((J.DEEP, J.FOUR_BANDS) if comb else J.SCRIPTS.values()):
             for ri in (0, 7):
-                blobs.append(J.progressive_with_script(bio.getvalue(), sc, ri))
+                blobs.append(J.progressive_with_script(bio.getvalue(), sc, ri, tables=tables))
+    if comb:
+        assert len(blobs) == 8 and all(max(b[b.index(b"\xff\xc4") + 5 + 15], b[b.index(b"\xff\xc4") + 5 + 14]) for b in blobs)     # 15- / 16-bit codes in the first table
+        return blobs
     bio = io.BytesIO(); Image.fromarray(gen.synth_rgb(90, 70, 32)).convert("L").save(bio, "JPEG", quality=80)
     blobs.append(J.progressive_with_script(bio.getvalue(), J.GREY, 0)); blobs.append(J.progressive_with_script(bio.getvalue(), J.GREY, 3))
     return blobs
@@ -494,13 +500,28 @@ def _scripted_files():
 def test_device_progressive_scan_scripts(hip, progressive_mode):
     """arbitrary scan scripts in one batch: scans that line up (unit u of a scan follows unit u of the scans it stands on, a few dozen units
     behind) next to files whose scans do not (a per-file barrier per level instead): == the oracle's feeder, coefficient for coefficient"""
-    blobs = _scripted_files()
+    blobs = _scripted_files() + _scripted_files("comb")
     rc, hst, st, res = _entropy_decode_device(hip, blobs)
     assert rc == 0 and hst == [0] * len(blobs) and not st.any(), hip.gamut_hip_last_error()
     for k, (data, (co, zz, info)) in enumerate(zip(blobs, res)):
         d = O.DecodedJpeg(data)
         assert np.array_equal(co, d.coeffs), (k, np.count_nonzero(co != d.coeffs))
         assert np.array_equal(zz, d.max_zag), k
+
+
+def test_device_progressive_comb_tables_come_out_of_the_scan_kernel(hip):
+    """a file k_prog_scan flags is decoded again by the host feeder, which would hide a kernel that flags what it should decode: with that second
+    reading switched off (GAMUT_HIP_JPEG_HOST_REDO=0) and every scan on the GPU, the comb-table files still come back OK and == the oracle"""
+    blobs = _scripted_files("comb")
+    os.environ["GAMUT_HIP_JPEG_PROGRESSIVE"] = "device"; os.environ["GAMUT_HIP_JPEG_HOST_REDO"] = "0"
+    try:
+        rc, hst, st, res = _entropy_decode_device(hip, blobs)
+    finally:
+        del os.environ["GAMUT_HIP_JPEG_PROGRESSIVE"]; del os.environ["GAMUT_HIP_JPEG_HOST_REDO"]
+    assert rc == 0 and hst == [0] * len(blobs) and not st.any(), (hst, hip.gamut_hip_last_error())
+    for k, (data, (co, zz, info)) in enumerate(zip(blobs, res)):
+        d = O.DecodedJpeg(data)
+        assert np.array_equal(co, d.coeffs) and np.array_equal(zz, d.max_zag), k
 
 
 def test_device_progressive_damaged_scan_that_leaves_its_band(hip, progressive_mode):
