@@ -193,32 +193,6 @@ bool allocatePixelStorage(uint8_t* existing, int type, int layers, int width, in
     return true;
 }
 
-// The device-image tail of every save_*: the pixels are encoded where they are, into the thread's encode scratch (`bound` bytes), and
-// the stream comes back in malloc memory.  encode(out, &n, stream) is the codec's batch entry on a batch of one at out_offset 0.
-template <class Encode> uint8_t* encode_device_image(size_t bound, size_t* len, Encode encode)
-{
-    hipStream_t st = thread_stream();
-    uint8_t* d = encode_staging(bound, 0, st, nullptr);
-    if (!d) return nullptr;
-    int64_t n = 0;
-    if (encode(d, &n, st) != GAMUT_HIP_OK || n <= 0) return nullptr;
-    uint8_t* r = (uint8_t*)malloc((size_t)n);
-    if (!r) return nullptr;
-    if (hipMemcpyAsync(r, d, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); free(r); return nullptr;
-    }
-    *len = (size_t)n;
-    return r;
-}
-
-bool write_file(const char* path, const uint8_t* bytes, size_t n)
-{
-    FILE* f = fopen(path, "wb");
-    bool ok = f && fwrite(bytes, 1, n, f) == n;
-    if (f && fclose(f) != 0) ok = false;
-    return ok;
-}
-
 } // namespace
 
 // fields in the reference's declaration order (image.d:1573-1620)
@@ -337,11 +311,21 @@ struct gamut_image {
     }
 
     static uint8_t* dmalloc(size_t n) { void* p = nullptr; return hipMalloc(&p, n ? n : 1) == hipSuccess ? (uint8_t*)p : nullptr; }
-    // nbytes a decoder left in the device allocation `dev`: the pixels of a device image as they are; a host image gets a malloc'd
-    // copy and dev is freed.  NULL (and nothing left to free) when the copy cannot be had.
-    uint8_t* residentOrHostCopy(uint8_t* dev, size_t nbytes) const
+    // ONE image through a codec's batch entry: nbytes of HBM and decode(dev, &zero, &status), the entry on a batch of one at offset 0.
+    // The pixels stay in HBM; NULL, and nothing left to free, when the allocation or the decode fails.
+    template <class Decode> static uint8_t* decodeOneToDevice(size_t nbytes, Decode decode)
     {
-        if (_device) return dev;
+        uint8_t* dev = dmalloc(nbytes);
+        const int64_t zero = 0; int status = 0;
+        if (dev && decode(dev, &zero, &status) != GAMUT_HIP_OK) { (void)hipFree(dev); dev = nullptr; }
+        return dev;
+    }
+    // The same with the pixels handed over where the image keeps them.  The decode is the GPU's either way: a device image keeps the
+    // allocation (its rows are tight), a host image gets a malloc'd copy and the allocation is freed.  NULL when any step fails.
+    template <class Decode> uint8_t* decodeOne(size_t nbytes, Decode decode) const
+    {
+        uint8_t* dev = decodeOneToDevice(nbytes, decode);
+        if (_device || !dev) return dev;
         uint8_t* host = (uint8_t*)malloc(nbytes ? nbytes : 1);
         const bool ok = host && gamut_hip_memcpy_d2h(host, dev, nbytes, nullptr) == GAMUT_HIP_OK && gamut_hip_stream_synchronize(nullptr) == GAMUT_HIP_OK;
         (void)hipFree(dev);
@@ -412,13 +396,14 @@ struct gamut_image {
         uint8_t* decoded = nullptr;
         if (_device) {                                                                      // stbi_load(_16) with the result left in HBM
             gamut_hip_png_info hd, info;
-            if (gamut_hip_png_read_header(bytes, len, &hd) == GAMUT_HIP_OK) {
-                const int64_t zero = 0; int st = 0;
-                decoded = dmalloc((size_t)hd.width * hd.height * 4 * (to16 ? 2 : 1) + 64);          // room for any channel count
-                if (decoded && gamut_hip_png_decode_batch_device(&bytes, &len, 1, requested, to16 ? 16 : 8, &zero, decoded, &info, &st, 1, nullptr) == GAMUT_HIP_OK) {
-                    w = (int)info.width; h = (int)info.height; comps = info.channels_in_file;
-                    ppmX = info.pixels_per_meter_x; ppmY = info.pixels_per_meter_y; ratio = info.pixel_aspect_ratio;
-                } else { if (decoded) (void)hipFree(decoded); decoded = nullptr; }
+            if (gamut_hip_png_read_header(bytes, len, &hd) == GAMUT_HIP_OK)
+                decoded = decodeOneToDevice((size_t)hd.width * hd.height * 4 * (to16 ? 2 : 1) + 64,    // room for any channel count
+                                            [&](uint8_t* dev, const int64_t* zero, int* st) {
+                    return gamut_hip_png_decode_batch_device(&bytes, &len, 1, requested, to16 ? 16 : 8, zero, dev, &info, st, 1, nullptr);
+                });
+            if (decoded) {
+                w = (int)info.width; h = (int)info.height; comps = info.channels_in_file;
+                ppmX = info.pixels_per_meter_x; ppmY = info.pixels_per_meter_y; ratio = info.pixel_aspect_ratio;
             }
         } else {
             decoded = to16 ? (uint8_t*)gamut_hip_stbi_load_16_from_memory(bytes, len, &w, &h, &comps, requested, &ppmX, &ppmY, &ratio)
@@ -439,14 +424,12 @@ struct gamut_image {
         gamut_hip_qoi_desc desc;
         uint8_t* decoded = nullptr;
         if (_device) {
-            const int size = (int)len; const int64_t zero = 0; int st = 0;
-            if (gamut_hip_qoi_read_header(bytes, size, &desc) == GAMUT_HIP_OK) {
-                decoded = dmalloc((size_t)desc.width * desc.height * (requested ? requested : desc.channels));
-                if (!decoded || gamut_hip_qoi_decode_batch_device(&bytes, &size, 1, requested, &zero, decoded, &desc, &st, nullptr) != GAMUT_HIP_OK) {
-                    if (decoded) (void)hipFree(decoded);
-                    decoded = nullptr;
-                }
-            }
+            const int size = (int)len;
+            if (gamut_hip_qoi_read_header(bytes, size, &desc) == GAMUT_HIP_OK)
+                decoded = decodeOneToDevice((size_t)desc.width * desc.height * (requested ? requested : desc.channels),
+                                            [&](uint8_t* dev, const int64_t* zero, int* st) {
+                    return gamut_hip_qoi_decode_batch_device(&bytes, &size, 1, requested, zero, dev, &desc, st, nullptr);
+                });
         } else decoded = (uint8_t*)gamut_hip_qoi_decode(bytes, (int)len, &desc, requested);
         if (!decoded) { error(kStrImageDecodingFailed); return; }
         if (!imageIsValidSize(1, (int)desc.width, (int)desc.height)) { error(kStrImageTooLarge); release(decoded); return; }
@@ -466,15 +449,9 @@ struct gamut_image {
         // qoix_lz4_decode :112: the flags are only validated, decodedType = streamType; a sub-codec that is not built yet fails the same way
         if (!validLoadFlags(flags) || gamut_hip_qoix_read_header(bytes, len, &hd) != GAMUT_HIP_OK) { error(kStrImageDecodingFailed); return; }
         const int comps = hd.channels;
-        const size_t nbytes = (size_t)hd.width * hd.height * comps;
-        // the decode is the GPU's either way: a device image keeps the allocation (its rows are tight), a host image gets the pixels copied back
-        uint8_t* dev = dmalloc(nbytes);
-        const int64_t zero = 0; int st = 0;
-        if (!dev || gamut_hip_qoix_decode_batch_device(&bytes, &len, 1, 0, &zero, dev, &info, &st, nullptr) != GAMUT_HIP_OK) {
-            if (dev) (void)hipFree(dev);
-            error(kStrImageDecodingFailed); return;
-        }
-        uint8_t* decoded = residentOrHostCopy(dev, nbytes);
+        uint8_t* decoded = decodeOne((size_t)hd.width * hd.height * comps, [&](uint8_t* dev, const int64_t* zero, int* st) {
+            return gamut_hip_qoix_decode_batch_device(&bytes, &len, 1, 0, zero, dev, &info, st, nullptr);
+        });
         if (!decoded) { error(kStrImageDecodingFailed); return; }
         if (!imageIsValidSize(1, hd.width, hd.height)) { error(kStrImageTooLarge); release(decoded); return; }     // :122-127
         adopt(decoded, hd.width, hd.height, hd.pixel_type, comps, hd.pixel_aspect_ratio, hd.resolution_y);          // :129-142, pitch = width * channels
@@ -489,15 +466,9 @@ struct gamut_image {
         gamut_hip_bmp_info hd, info;
         if (gamut_hip_bmp_read_header(bytes, len, &hd) != GAMUT_HIP_OK) { error(kStrImageDecodingFailed); return; }
         const int comps = requested ? requested : hd.channels_in_file;
-        const size_t nbytes = (size_t)hd.width * hd.height * comps;
-        // the decode is the GPU's either way; a host image gets the pixels copied back from a staging allocation
-        uint8_t* dev = dmalloc(nbytes);
-        const int64_t zero = 0; int st = 0;
-        if (!dev || gamut_hip_bmp_decode_batch_device(&bytes, &len, 1, requested, &zero, dev, &info, &st, nullptr) != GAMUT_HIP_OK) {
-            if (dev) (void)hipFree(dev);
-            error(kStrImageDecodingFailed); return;
-        }
-        uint8_t* decoded = residentOrHostCopy(dev, nbytes);
+        uint8_t* decoded = decodeOne((size_t)hd.width * hd.height * comps, [&](uint8_t* dev, const int64_t* zero, int* st) {
+            return gamut_hip_bmp_decode_batch_device(&bytes, &len, 1, requested, zero, dev, &info, st, nullptr);
+        });
         if (!decoded) { error(kStrImageDecodingFailed); return; }
         if (!imageIsValidSize(1, info.width, info.height)) { error(kStrImageTooLarge); release(decoded); return; }
         adopt(decoded, info.width, info.height, kType8[comps], comps, info.pixel_aspect_ratio == -1 ? -1.0f : info.pixel_aspect_ratio,
@@ -512,15 +483,9 @@ struct gamut_image {
         if (!imageIsValidSize(1, hd.width, hd.height)) { error(kStrImageTooLarge); return; } // :57-61
         if (hrc != GAMUT_HIP_OK) { error(kStrImageDecodingFailed); return; }                // decodeImage's header part :63-71
         const int comps = hd.channels_in_file;                                              // the file's own type; the flags act in convertTo
-        const size_t nbytes = (size_t)hd.width * hd.height * comps;
-        // the decode is the GPU's either way; a host image gets the pixels copied back from a staging allocation
-        uint8_t* dev = dmalloc(nbytes);
-        const int64_t zero = 0; int st = 0;
-        if (!dev || gamut_hip_tga_decode_batch_device(&bytes, &len, 1, 0, &zero, dev, &info, &st, nullptr) != GAMUT_HIP_OK) {
-            if (dev) (void)hipFree(dev);
-            error(kStrImageDecodingFailed); return;
-        }
-        uint8_t* decoded = residentOrHostCopy(dev, nbytes);
+        uint8_t* decoded = decodeOne((size_t)hd.width * hd.height * comps, [&](uint8_t* dev, const int64_t* zero, int* st) {
+            return gamut_hip_tga_decode_batch_device(&bytes, &len, 1, 0, zero, dev, &info, st, nullptr);
+        });
         if (!decoded) { error(kStrImageDecodingFailed); return; }
         adopt(decoded, hd.width, hd.height, kType8[comps], comps, -1.0f, -1.0f);                // :87-88 GAMUT_UNKNOWN_ASPECT_RATIO / _RESOLUTION
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);                           // :94
@@ -532,14 +497,9 @@ struct gamut_image {
         if (gamut_hip_sqz_read_header(bytes, len, &hd) != GAMUT_HIP_OK) { error(kStrImageDecodingIOFailure); return; }
         const size_t nbytes = (size_t)hd.width * hd.height * hd.planes;
         if (hd.width > MAX_W || hd.height > MAX_H || (long long)nbytes > MAX_BYTES) { error(kStrImageTooLarge); return; }      // :88-94 (16-bit sides never get here)
-        // the decode is the GPU's either way: a device image keeps the allocation (its rows are tight), a host image gets the pixels copied back
-        uint8_t* dev = dmalloc(nbytes);
-        const int64_t zero = 0; int st = 0;
-        if (!dev || gamut_hip_sqz_decode_batch_device(&bytes, &len, 1, &zero, dev, &info, &st, nullptr) != GAMUT_HIP_OK) {          // :112-118
-            if (dev) (void)hipFree(dev);
-            error(kStrImageDecodingIOFailure); return;
-        }
-        uint8_t* decoded = residentOrHostCopy(dev, nbytes);
+        uint8_t* decoded = decodeOne(nbytes, [&](uint8_t* dev, const int64_t* zero, int* st) {                                   // :112-118
+            return gamut_hip_sqz_decode_batch_device(&bytes, &len, 1, zero, dev, &info, st, nullptr);
+        });
         if (!decoded) { error(kStrImageDecodingIOFailure); return; }
         adopt(decoded, hd.width, hd.height, hd.pixel_type, hd.planes, -1.0f, -1.0f);            // :120-129 l8 / rgb8, GAMUT_UNKNOWN_ASPECT_RATIO / _RESOLUTION
         _layoutConstraints = 0;                                                             // :127
@@ -581,6 +541,227 @@ struct gamut_image {
         convertTo(applyLoadFlags(_type, flags), flags & 0xFFFF);                           // :102, over all layers
     }
 };
+
+namespace {
+
+// ---- saving (image.d:940-1011): saveToStream -> g_plugins[fif].saveProc.  A saver states what its format refuses and names the codec's
+// two calls on one image, the host drop-in and the device batch entry; encode_image, save_to_memory and save_to_file do the rest. ----
+using Saver = uint8_t* (*)(gamut_image* img, int flags, size_t* len);           // -> the malloc'd file, *len bytes, or NULL: refused or failed
+
+// a pixel type's channel count when it is one of l8 / la8 / rgb8 / rgba8 (l16 / la16 / rgb16 / rgba16 for channels16), else 0
+int channels8(int type)
+{
+    return type == GAMUT_PIXEL_l8 ? 1 : type == GAMUT_PIXEL_la8 ? 2 : type == GAMUT_PIXEL_rgb8 ? 3 : type == GAMUT_PIXEL_rgba8 ? 4 : 0;
+}
+int channels16(int type) { return type % 3 == 1 ? channels8(type - 1) : 0; }
+
+// a batch of one for a codec's *_encode_batch_device: the image's pixels where they are, the file at out_offset 0 of the thread's encode scratch
+struct OneImage { const uint8_t* src; int64_t pitch, layer_offset, out_offset; uint8_t* out; int64_t len; int status; hipStream_t stream; };
+
+// the malloc'd file a host drop-in returned, its int length handed over
+uint8_t* host_file(void* file, int n, size_t* len)
+{
+    if (file) *len = (size_t)n;
+    return (uint8_t*)file;
+}
+// One image through its codec, wherever its pixels live.  host(&n) is the codec's drop-in on the host pixels (it stages them through pinned
+// memory); device(b) is the codec's batch entry on the batch of one `b`: device pixels are encoded where they are, into `bound` bytes of
+// the thread's encode scratch, and the stream comes back in malloc memory.
+template <class Host, class Device> uint8_t* encode_image(const gamut_image* img, size_t bound, size_t* len, Host host, Device device)
+{
+    if (!img->_device) { int n = 0; void* file = host(&n); return host_file(file, n, len); }
+    OneImage b{ img->_data, img->_pitch, img->_layerOffset, 0, nullptr, 0, 0, thread_stream() };
+    b.out = encode_staging(bound, 0, b.stream, nullptr);
+    if (!b.out) return nullptr;
+    if (device(b) != GAMUT_HIP_OK || b.len <= 0) return nullptr;
+    uint8_t* r = (uint8_t*)malloc((size_t)b.len);
+    if (!r) return nullptr;
+    if (hipMemcpyAsync(r, b.out, (size_t)b.len, hipMemcpyDeviceToHost, b.stream) != hipSuccess || hipStreamSynchronize(b.stream) != hipSuccess) {
+        (void)hipGetLastError(); free(r); return nullptr;
+    }
+    *len = (size_t)b.len;
+    return r;
+}
+
+// saveQOI (plugins/qoi.d:149-184): rgb8 / rgba8, QOI_SRGB; flags ignored
+uint8_t* save_qoi(gamut_image* img, int, size_t* len)
+{
+    gamut_hip_qoi_desc desc{};
+    desc.width = (uint32_t)img->_width; desc.height = (uint32_t)img->_height; desc.colorspace = 0;
+    desc.channels = channels8(img->_type);
+    if (desc.channels < 3 || gamut_hip_qoi_encode_bound(&desc) == 0) return nullptr;                    // the bound is 0 for what qoi_encode refuses
+    return encode_image(img, (size_t)gamut_hip_qoi_encode_bound(&desc), len,
+        [&](int* n) { return gamut_hip_qoi_encode(img->_data, &desc, img->_pitch, n); },
+        [&](OneImage& b) { return gamut_hip_qoi_encode_batch_device(&b.src, &b.pitch, &desc, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
+}
+
+// saveJPEG (plugins/jpeg.d:112-148): l8 -> 1 component, rgb8 -> 3, everything else (rgba8 included: stb would drop the alpha) refused;
+// quality 90 (4:2:0); flags ignored
+uint8_t* save_jpeg(gamut_image* img, int, size_t* len)
+{
+    const int32_t comp = channels8(img->_type), quality = 90, w = img->_width, h = img->_height;
+    if ((comp != 1 && comp != 3) || gamut_hip_jpeg_encode_bound(w, h, comp, quality) == 0) return nullptr;
+    return encode_image(img, (size_t)gamut_hip_jpeg_encode_bound(w, h, comp, quality), len,
+        [&](int* n) -> void* {                                 // the stbi_write_jpg_to_func drop-in, as saveJPEG calls it
+            struct Sink { std::vector<uint8_t> b; } sink;
+            auto put = [](void* ctx, const void* data, int size) {
+                Sink* s = (Sink*)ctx;
+                try { s->b.insert(s->b.end(), (const uint8_t*)data, (const uint8_t*)data + size); } catch (...) { s->b.clear(); }
+            };
+            if (!gamut_hip_jpeg_write_to_func(put, &sink, w, h, comp, img->_data, (int)img->_pitch, quality) || sink.b.empty()) return nullptr;
+            void* r = malloc(sink.b.size());
+            if (r) { memcpy(r, sink.b.data(), sink.b.size()); *n = (int)sink.b.size(); }
+            return r;
+        },
+        [&](OneImage& b) { return gamut_hip_jpeg_encode_batch_device(&b.src, &b.pitch, &w, &h, &comp, &quality, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
+}
+
+// savePNG (plugins/png.d:172-221): the eight integer types, flags read (:201-206), pitch passed through as stb's signed stride
+uint8_t* save_png(gamut_image* img, int flags, size_t* len)
+{
+    const int32_t is16 = channels16(img->_type) != 0, comp = is16 ? channels16(img->_type) : channels8(img->_type);
+    const int32_t force_filter = (flags & GAMUT_ENCODE_PNG_FILTER_FAST) ? 0 : -1, w = img->_width, h = img->_height;
+    int32_t level = flags & 15;
+    if (level == GAMUT_ENCODE_PNG_COMPRESSION_DEFAULT) level = GAMUT_ENCODE_PNG_COMPRESSION_5;
+    level--;
+    if (!comp || level < 0 || level > 10 || gamut_hip_png_encode_bound(w, h, comp, is16) == 0) return nullptr;
+    return encode_image(img, (size_t)gamut_hip_png_encode_bound(w, h, comp, is16), len,
+        [&](int* n) { return gamut_hip_png_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, n, is16, force_filter, level); },
+        [&](OneImage& b) { return gamut_hip_png_encode_batch_device(&b.src, &b.pitch, &w, &h, &comp, &is16, &force_filter, &level, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
+}
+
+// saveBMP (plugins/bmp.d:166-194) + write_bmp's density fields (bmpenc.d:63-74): rgb8 / rgba8, one layer, 1..32767 each way; flags ignored
+uint8_t* save_bmp(gamut_image* img, int, size_t* len)
+{
+    const int32_t comp = channels8(img->_type), w = img->_width, h = img->_height;
+    if (comp < 3 || img->_layerCount != 1 || gamut_hip_bmp_encode_bound(w, h, comp) == 0) return nullptr;
+    // pixelsPerMeterY = convertMetersToInches(dotsPerInchY), X through the aspect ratio (image.d:314-361)
+    int32_t ppm_x = 0, ppm_y = 0;
+    if (img->_resolutionY != -1) {
+        ppm_y = (int)roundf(img->_resolutionY * kInchesPerMeter);
+        if (img->_pixelAspectRatio != -1) ppm_x = (int)roundf(img->_resolutionY * img->_pixelAspectRatio * kInchesPerMeter);
+    }
+    return encode_image(img, (size_t)gamut_hip_bmp_encode_bound(w, h, comp), len,
+        [&](int* n) { return gamut_hip_bmp_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, ppm_x, ppm_y, n); },
+        [&](OneImage& b) { return gamut_hip_bmp_encode_batch_device(&b.src, &b.pitch, &w, &h, &comp, &ppm_x, &ppm_y, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
+}
+
+// saveGIF (plugins/gif.d:105-147): rgba8 only, every layer a frame of 7 centiseconds, maxBitDepth 16, alpha threshold 10; flags ignored
+uint8_t* save_gif(gamut_image* img, int, size_t* len)
+{
+    const int32_t w = img->_width, h = img->_height, frames = img->_layerCount;
+    if (img->_type != GAMUT_PIXEL_rgba8 || frames < 1) return nullptr;
+    if (gamut_hip_gif_encode_bound(w, h, frames) == 0) return nullptr;
+    return encode_image(img, (size_t)gamut_hip_gif_encode_bound(w, h, frames), len,
+        [&](int* n) { return gamut_hip_gif_write_to_mem(img->_data, (int)img->_pitch, (int64_t)img->_layerOffset, w, h, frames, 7, 16, 10, n); },
+        [&](OneImage& b) { return gamut_hip_gif_encode_batch_device(&b.src, &b.pitch, &b.layer_offset, &w, &h, &frames, nullptr, nullptr, nullptr, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
+}
+
+// saveTGA (plugins/tga.d:128-150): l8 / la8 / rgb8 / rgba8, scanptr(y) of layer 0 from the bottom row up, enableRLE = true; flags ignored
+uint8_t* save_tga(gamut_image* img, int, size_t* len)
+{
+    const int32_t comp = channels8(img->_type), w = img->_width, h = img->_height;
+    if (!comp || img->_layerCount < 1 || gamut_hip_tga_encode_bound(w, h, comp) == 0) return nullptr;
+    return encode_image(img, (size_t)gamut_hip_tga_encode_bound(w, h, comp), len,
+        [&](int* n) { return gamut_hip_tga_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, 1, n); },
+        [&](OneImage& b) { return gamut_hip_tga_encode_batch_device(&b.src, &b.pitch, &w, &h, &comp, nullptr, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
+}
+
+// saveQOIX (plugins/qoix.d:156-242), the 8-bit colour slice: rgb8 / rgba8 / rgbap8 (colorspace 2), layer 0, the image's pixel aspect
+// ratio and vertical DPI in the header, LZ4 when it is smaller; grey and 16-bit types wait for their codecs; flags ignored
+uint8_t* save_qoix(gamut_image* img, int, size_t* len)
+{
+    gamut_hip_qoix_desc d{};
+    d.width = img->_width; d.height = img->_height;
+    d.channels = img->_type == GAMUT_PIXEL_rgbap8 ? 4 : channels8(img->_type) >= 3 ? channels8(img->_type) : 0;
+    d.colorspace = img->_type == GAMUT_PIXEL_rgbap8 ? 2 : 0;
+    d.mode = 0;
+    d.pixel_aspect_ratio = img->_pixelAspectRatio; d.resolution_y = img->_resolutionY;
+    if (!d.channels || img->_layerCount < 1 || gamut_hip_qoix_encode_bound(&d) < 0) return nullptr;
+    return encode_image(img, (size_t)gamut_hip_qoix_encode_bound(&d), len,
+        [&](int* n) { return gamut_hip_qoix_write_to_mem(img->_data, (int)img->_pitch, &d, n); },
+        [&](OneImage& b) { return gamut_hip_qoix_encode_batch_device(&b.src, &b.pitch, &d, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
+}
+
+// saveDDS (plugins/dds.d:47-216): l8 / la8 / rgb8 / rgba8, scanline(y) of layer 0, BC7 blocks behind a DX10 header; flags ignored
+uint8_t* save_dds(gamut_image* img, int, size_t* len)
+{
+    const int32_t comp = channels8(img->_type), w = img->_width, h = img->_height;
+    if (!comp || img->_layerCount < 1 || gamut_hip_dds_encode_bound(w, h, comp) == 0) return nullptr;
+    return encode_image(img, (size_t)gamut_hip_dds_encode_bound(w, h, comp), len,
+        [&](int* n) { return gamut_hip_dds_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, n); },
+        [&](OneImage& b) { return gamut_hip_dds_encode_batch_device(&b.src, &b.pitch, &w, &h, &comp, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
+}
+
+// saveSQZ (plugins/sqz.d:141-201): rgb8 only, sides of at least 8, scanptr(0) of layer 0; Oklab, 7 levels (clamped to what the size
+// admits), chroma one round later, snake scan; the byte budget comes from the flags and the file is the bytes used, not the budget.
+// false: refused.
+bool sqz_encode_desc(const gamut_image* img, int flags, gamut_hip_sqz_encode_desc* d)
+{
+    const int w = img->_width, h = img->_height;
+    if (w < 8 || h < 8 || w > 65535 || h > 65535 || img->_type != GAMUT_PIXEL_rgb8 || img->_layerCount < 1) return false;
+    *d = gamut_hip_sqz_encode_desc{};
+    d->width = w; d->height = h; d->color_mode = 2; d->levels = 7; d->scan_order = 1; d->subsampling = 1;
+    d->budget = gamut_hip_sqz_budget_from_flags(w, h, flags);
+    return true;
+}
+uint8_t* save_sqz(gamut_image* img, int flags, size_t* len)
+{
+    gamut_hip_sqz_encode_desc d;
+    if (!sqz_encode_desc(img, flags, &d)) return nullptr;
+    if (!img->_device) { int n = 0; void* file = gamut_hip_sqz_write_to_mem(img->_data, (int)img->_pitch, &d, &n); return host_file(file, n, len); }
+    uint8_t* file = (uint8_t*)malloc((size_t)d.budget);               // a host buffer for either writer (gamut_hip_sqz_set_writer): the device writer's file is downloaded into it
+    if (!file) return nullptr;
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    if (gamut_hip_sqz_encode_batch_device(&src, &pitch, &d, 1, &off, file, &n, &status, nullptr) != GAMUT_HIP_OK) { free(file); return nullptr; }
+    if (void* shrunk = realloc(file, (size_t)n)) file = (uint8_t*)shrunk;
+    *len = (size_t)n;
+    return file;
+}
+
+// saveSQZ with the file left in HBM: device-resident rgb8 images only (a host image has no business there: save_sqz_to_memory)
+uint8_t* save_sqz_to_device(gamut_image* img, int flags, size_t* len)
+{
+    gamut_hip_sqz_encode_desc d;
+    if (!img->_device || !sqz_encode_desc(img, flags, &d)) return nullptr;
+    if (img->_deviceFile) { (void)hipFree(img->_deviceFile); img->_deviceFile = nullptr; }
+    uint8_t* file = nullptr;
+    if (hipMalloc((void**)&file, (size_t)d.budget) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
+    if (gamut_hip_sqz_encode_batch_to_device(&src, &pitch, &d, 1, &off, file, &n, &status, nullptr) != GAMUT_HIP_OK) { (void)hipFree(file); return nullptr; }
+    img->_deviceFile = file;
+    *len = (size_t)n;
+    return file;
+}
+
+// the generic entry dispatches these three (image.d:966-980); every other format has entries of its own
+Saver generic_saver(int fif)
+{
+    return fif == GAMUT_FORMAT_QOI ? save_qoi : fif == GAMUT_FORMAT_JPEG ? save_jpeg : fif == GAMUT_FORMAT_GIF ? save_gif : nullptr;
+}
+
+// what every gamut_image_save_*_to_memory is: the file in malloc memory, or NULL and *len = 0
+uint8_t* save_to_memory(Saver save, gamut_image* img, int flags, size_t* len)
+{
+    if (len) *len = 0;
+    if (!img || !len || !img->isValid() || !img->_data || !save) return nullptr;
+    return save(img, flags, len);
+}
+// what every gamut_image_save_*_to_file is; nothing is created when the image is refused
+int save_to_file(Saver save, gamut_image* img, const char* path, int flags)
+{
+    if (!path) return 0;
+    size_t n = 0;
+    uint8_t* encoded = save_to_memory(save, img, flags, &n);
+    if (!encoded) return 0;
+    FILE* f = fopen(path, "wb");
+    bool ok = f && fwrite(encoded, 1, n, f) == n;
+    if (f && fclose(f) != 0) ok = false;
+    free(encoded);
+    return ok;
+}
+
+} // namespace
 
 static int identify(const uint8_t* b, size_t len)
 {
@@ -773,369 +954,22 @@ int gamut_image_copy_pixels_to_host(gamut_image* img, int layer, void* dst, int6
     return 1;
 }
 
-// ---- saving (image.d:940-1011): saveToStream -> g_plugins[fif].saveProc; saveQOI (plugins/qoi.d:149-184) and saveJPEG
-// (plugins/jpeg.d:112-148) have encoders here; savePNG (plugins/png.d:172-221) has entries of its own further down ----
-static uint8_t* save_qoi(gamut_image* img, size_t* len)
-{
-    gamut_hip_qoi_desc desc{};
-    desc.width = (uint32_t)img->_width; desc.height = (uint32_t)img->_height; desc.colorspace = 0;       // QOI_SRGB
-    if (img->_type == GAMUT_PIXEL_rgb8) desc.channels = 3;
-    else if (img->_type == GAMUT_PIXEL_rgba8) desc.channels = 4;
-    else return nullptr;
-    if (gamut_hip_qoi_encode_bound(&desc) == 0) return nullptr;                                         // what qoi_encode refuses
-    if (!img->_device) {                                       // host pixels: the drop-in stages them through pinned memory
-        int n = 0;
-        uint8_t* r = (uint8_t*)gamut_hip_qoi_encode(img->_data, &desc, img->_pitch, &n);
-        if (r) *len = (size_t)n;
-        return r;
-    }
-    // device pixels: encoded where they are, the stream comes back
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
-    return encode_device_image((size_t)gamut_hip_qoi_encode_bound(&desc), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
-        return gamut_hip_qoi_encode_batch_device(&src, &pitch, &desc, 1, &off, d, n, &status, st);
-    });
-}
-
-// saveJPEG: l8 -> 1 component, rgb8 -> 3, everything else (rgba8 included: stb would drop the alpha) refused; quality 90 (4:2:0)
-static uint8_t* save_jpeg(gamut_image* img, size_t* len)
-{
-    int comp;
-    if (img->_type == GAMUT_PIXEL_l8) comp = 1;
-    else if (img->_type == GAMUT_PIXEL_rgb8) comp = 3;
-    else return nullptr;
-    const int quality = 90, w = img->_width, h = img->_height;
-    if (gamut_hip_jpeg_encode_bound(w, h, comp, quality) == 0) return nullptr;
-    if (!img->_device) {                                       // host pixels: the stbi_write_jpg_to_func drop-in, as saveJPEG calls it
-        struct Sink { std::vector<uint8_t> b; } sink;
-        auto put = [](void* ctx, const void* data, int size) {
-            Sink* s = (Sink*)ctx;
-            try { s->b.insert(s->b.end(), (const uint8_t*)data, (const uint8_t*)data + size); } catch (...) { s->b.clear(); }
-        };
-        if (!gamut_hip_jpeg_write_to_func(put, &sink, w, h, comp, img->_data, (int)img->_pitch, quality) || sink.b.empty()) return nullptr;
-        uint8_t* r = (uint8_t*)malloc(sink.b.size());
-        if (!r) return nullptr;
-        memcpy(r, sink.b.data(), sink.b.size());
-        *len = sink.b.size();
-        return r;
-    }
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
-    const int32_t W = w, H = h, Cc = comp, Q = quality;
-    return encode_device_image((size_t)gamut_hip_jpeg_encode_bound(w, h, comp, quality), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
-        return gamut_hip_jpeg_encode_batch_device(&src, &pitch, &W, &H, &Cc, &Q, 1, &off, d, n, &status, st);
-    });
-}
-
-// savePNG (plugins/png.d:172-221): the eight integer types, flags read (:201-206), pitch passed through as stb's signed stride
-static uint8_t* save_png(gamut_image* img, int flags, size_t* len)
-{
-    int comp, is16 = 0;
-    switch (img->_type) {
-        case GAMUT_PIXEL_l8: comp = 1; break;
-        case GAMUT_PIXEL_la8: comp = 2; break;
-        case GAMUT_PIXEL_rgb8: comp = 3; break;
-        case GAMUT_PIXEL_rgba8: comp = 4; break;
-        case GAMUT_PIXEL_l16: comp = 1; is16 = 1; break;
-        case GAMUT_PIXEL_la16: comp = 2; is16 = 1; break;
-        case GAMUT_PIXEL_rgb16: comp = 3; is16 = 1; break;
-        case GAMUT_PIXEL_rgba16: comp = 4; is16 = 1; break;
-        default: return nullptr;
-    }
-    const int force_filter = (flags & GAMUT_ENCODE_PNG_FILTER_FAST) ? 0 : -1;
-    int level = flags & 15;
-    if (level == GAMUT_ENCODE_PNG_COMPRESSION_DEFAULT) level = GAMUT_ENCODE_PNG_COMPRESSION_5;
-    level--;
-    const int w = img->_width, h = img->_height;
-    if (level < 0 || level > 10 || gamut_hip_png_encode_bound(w, h, comp, is16) == 0) return nullptr;
-    if (!img->_device) {                                       // host pixels: the stbi_write_png_to_mem drop-in, as savePNG calls it
-        int n = 0;
-        uint8_t* r = (uint8_t*)gamut_hip_png_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, &n, is16, force_filter, level);
-        if (r) *len = (size_t)n;
-        return r;
-    }
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
-    const int32_t W = w, H = h, Cc = comp, S = is16, F = force_filter, Lv = level;
-    return encode_device_image((size_t)gamut_hip_png_encode_bound(w, h, comp, is16), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
-        return gamut_hip_png_encode_batch_device(&src, &pitch, &W, &H, &Cc, &S, &F, &Lv, 1, &off, d, n, &status, st);
-    });
-}
-
-uint8_t* gamut_image_save_png_to_memory(gamut_image* img, int flags, size_t* len)
-{
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
-    return save_png(img, flags, len);
-}
-int gamut_image_save_png_to_file(gamut_image* img, const char* path, int flags)
-{
-    if (!path) return 0;
-    size_t n = 0;
-    uint8_t* enc = gamut_image_save_png_to_memory(img, flags, &n);
-    if (!enc) return 0;
-    const bool ok = write_file(path, enc, n);
-    free(enc);
-    return ok;
-}
-
-// saveBMP (plugins/bmp.d:166-194) + write_bmp's density fields (bmpenc.d:63-74): rgb8 / rgba8, one layer, 1..32767 each way
-static uint8_t* save_bmp(gamut_image* img, size_t* len)
-{
-    const int comp = img->_type == GAMUT_PIXEL_rgb8 ? 3 : img->_type == GAMUT_PIXEL_rgba8 ? 4 : 0;
-    const int w = img->_width, h = img->_height;
-    if (!comp || img->_layerCount != 1 || gamut_hip_bmp_encode_bound(w, h, comp) == 0) return nullptr;
-    // pixelsPerMeterY = convertMetersToInches(dotsPerInchY), X through the aspect ratio (image.d:314-361)
-    int ppm_x = 0, ppm_y = 0;
-    if (img->_resolutionY != -1) {
-        ppm_y = (int)roundf(img->_resolutionY * kInchesPerMeter);
-        if (img->_pixelAspectRatio != -1) ppm_x = (int)roundf(img->_resolutionY * img->_pixelAspectRatio * kInchesPerMeter);
-    }
-    if (!img->_device) {
-        int n = 0;
-        uint8_t* r = (uint8_t*)gamut_hip_bmp_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, ppm_x, ppm_y, &n);
-        if (r) *len = (size_t)n;
-        return r;
-    }
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
-    const int32_t W = w, H = h, Cc = comp, PX = ppm_x, PY = ppm_y;
-    return encode_device_image((size_t)gamut_hip_bmp_encode_bound(w, h, comp), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
-        return gamut_hip_bmp_encode_batch_device(&src, &pitch, &W, &H, &Cc, &PX, &PY, 1, &off, d, n, &status, st);
-    });
-}
-
-// saveGIF (plugins/gif.d:105-147): rgba8 only, every layer a frame of 7 centiseconds, maxBitDepth 16, alpha threshold 10
-static uint8_t* save_gif(gamut_image* img, size_t* len)
-{
-    const int w = img->_width, h = img->_height, frames = img->_layerCount;
-    if (img->_type != GAMUT_PIXEL_rgba8 || frames < 1) return nullptr;
-    const int64_t bound = gamut_hip_gif_encode_bound(w, h, frames);
-    if (bound == 0) return nullptr;
-    if (!img->_device) {
-        int n = 0;
-        uint8_t* r = (uint8_t*)gamut_hip_gif_write_to_mem(img->_data, (int)img->_pitch, (int64_t)img->_layerOffset, w, h, frames, 7, 16, 10, &n);
-        if (r) *len = (size_t)n;
-        return r;
-    }
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, layer = img->_layerOffset, off = 0; int status = 0;
-    const int32_t W = w, H = h, F = frames;
-    return encode_device_image((size_t)bound, len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
-        return gamut_hip_gif_encode_batch_device(&src, &pitch, &layer, &W, &H, &F, nullptr, nullptr, nullptr, 1, &off, d, n, &status, st);
-    });
-}
-
-uint8_t* gamut_image_save_bmp_to_memory(gamut_image* img, int flags, size_t* len)
-{
-    (void)flags;                                               // saveBMP ignores them
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
-    return save_bmp(img, len);
-}
-int gamut_image_save_bmp_to_file(gamut_image* img, const char* path, int flags)
-{
-    if (!path) return 0;
-    size_t n = 0;
-    uint8_t* enc = gamut_image_save_bmp_to_memory(img, flags, &n);
-    if (!enc) return 0;
-    const bool ok = write_file(path, enc, n);
-    free(enc);
-    return ok;
-}
-
-// saveTGA (plugins/tga.d:128-150): l8 / la8 / rgb8 / rgba8, scanptr(y) of layer 0 from the bottom row up, enableRLE = true
-static uint8_t* save_tga(gamut_image* img, size_t* len)
-{
-    const int comp = img->_type == GAMUT_PIXEL_l8 ? 1 : img->_type == GAMUT_PIXEL_la8 ? 2 : img->_type == GAMUT_PIXEL_rgb8 ? 3 :
-                     img->_type == GAMUT_PIXEL_rgba8 ? 4 : 0;
-    const int w = img->_width, h = img->_height;
-    if (!comp || img->_layerCount < 1 || gamut_hip_tga_encode_bound(w, h, comp) == 0) return nullptr;
-    if (!img->_device) {
-        int n = 0;
-        uint8_t* r = (uint8_t*)gamut_hip_tga_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, 1, &n);
-        if (r) *len = (size_t)n;
-        return r;
-    }
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
-    const int32_t W = w, H = h, Cc = comp;
-    return encode_device_image((size_t)gamut_hip_tga_encode_bound(w, h, comp), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
-        return gamut_hip_tga_encode_batch_device(&src, &pitch, &W, &H, &Cc, nullptr, 1, &off, d, n, &status, st);
-    });
-}
-
-uint8_t* gamut_image_save_tga_to_memory(gamut_image* img, int flags, size_t* len)
-{
-    (void)flags;                                               // saveTGA ignores them
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
-    return save_tga(img, len);
-}
-int gamut_image_save_tga_to_file(gamut_image* img, const char* path, int flags)
-{
-    if (!path) return 0;
-    size_t n = 0;
-    uint8_t* enc = gamut_image_save_tga_to_memory(img, flags, &n);
-    if (!enc) return 0;
-    const bool ok = write_file(path, enc, n);
-    free(enc);
-    return ok;
-}
-
-// saveQOIX (plugins/qoix.d:156-242), the 8-bit colour slice: rgb8 / rgba8 / rgbap8 (colorspace 2), layer 0, the image's pixel aspect
-// ratio and vertical DPI in the header, LZ4 when it is smaller; grey and 16-bit types wait for their codecs
-static uint8_t* save_qoix(gamut_image* img, size_t* len)
-{
-    gamut_hip_qoix_desc d{};
-    d.width = img->_width; d.height = img->_height;
-    d.channels = img->_type == GAMUT_PIXEL_rgb8 ? 3 : img->_type == GAMUT_PIXEL_rgba8 || img->_type == GAMUT_PIXEL_rgbap8 ? 4 : 0;
-    d.colorspace = img->_type == GAMUT_PIXEL_rgbap8 ? 2 : 0;
-    d.mode = 0;
-    d.pixel_aspect_ratio = img->_pixelAspectRatio; d.resolution_y = img->_resolutionY;
-    if (!d.channels || img->_layerCount < 1 || gamut_hip_qoix_encode_bound(&d) < 0) return nullptr;
-    if (!img->_device) {
-        int n = 0;
-        uint8_t* r = (uint8_t*)gamut_hip_qoix_write_to_mem(img->_data, (int)img->_pitch, &d, &n);
-        if (r) *len = (size_t)n;
-        return r;
-    }
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
-    return encode_device_image((size_t)gamut_hip_qoix_encode_bound(&d), len, [&](uint8_t* dev, int64_t* n, hipStream_t st) {
-        return gamut_hip_qoix_encode_batch_device(&src, &pitch, &d, 1, &off, dev, n, &status, st);
-    });
-}
-
-uint8_t* gamut_image_save_qoix_to_memory(gamut_image* img, int flags, size_t* len)
-{
-    (void)flags;                                               // saveQOIX ignores them
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
-    return save_qoix(img, len);
-}
-int gamut_image_save_qoix_to_file(gamut_image* img, const char* path, int flags)
-{
-    if (!path) return 0;
-    size_t n = 0;
-    uint8_t* enc = gamut_image_save_qoix_to_memory(img, flags, &n);
-    if (!enc) return 0;
-    const bool ok = write_file(path, enc, n);
-    free(enc);
-    return ok;
-}
-
-// saveDDS (plugins/dds.d:47-216): l8 / la8 / rgb8 / rgba8, scanline(y) of layer 0, BC7 blocks behind a DX10 header
-static uint8_t* save_dds(gamut_image* img, size_t* len)
-{
-    const int comp = img->_type == GAMUT_PIXEL_l8 ? 1 : img->_type == GAMUT_PIXEL_la8 ? 2 : img->_type == GAMUT_PIXEL_rgb8 ? 3 :
-                     img->_type == GAMUT_PIXEL_rgba8 ? 4 : 0;
-    const int w = img->_width, h = img->_height;
-    if (!comp || img->_layerCount < 1 || gamut_hip_dds_encode_bound(w, h, comp) == 0) return nullptr;
-    if (!img->_device) {
-        int n = 0;
-        uint8_t* r = (uint8_t*)gamut_hip_dds_write_to_mem(img->_data, (int)img->_pitch, w, h, comp, &n);
-        if (r) *len = (size_t)n;
-        return r;
-    }
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int status = 0;
-    const int32_t W = w, H = h, Cc = comp;
-    return encode_device_image((size_t)gamut_hip_dds_encode_bound(w, h, comp), len, [&](uint8_t* d, int64_t* n, hipStream_t st) {
-        return gamut_hip_dds_encode_batch_device(&src, &pitch, &W, &H, &Cc, 1, &off, d, n, &status, st);
-    });
-}
-
-uint8_t* gamut_image_save_dds_to_memory(gamut_image* img, int flags, size_t* len)
-{
-    (void)flags;                                               // saveDDS ignores them
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
-    return save_dds(img, len);
-}
-int gamut_image_save_dds_to_file(gamut_image* img, const char* path, int flags)
-{
-    if (!path) return 0;
-    size_t n = 0;
-    uint8_t* enc = gamut_image_save_dds_to_memory(img, flags, &n);
-    if (!enc) return 0;
-    const bool ok = write_file(path, enc, n);
-    free(enc);
-    return ok;
-}
-
-// saveSQZ (plugins/sqz.d:141-201): rgb8 only, sides of at least 8, scanptr(0) of layer 0; Oklab, 7 levels (clamped to what the size
-// admits), chroma one round later, snake scan; the byte budget comes from the flags and the file is the bytes used, not the budget
-static uint8_t* save_sqz(gamut_image* img, int flags, size_t* len)
-{
-    const int w = img->_width, h = img->_height;
-    if (w < 8 || h < 8 || w > 65535 || h > 65535 || img->_type != GAMUT_PIXEL_rgb8 || img->_layerCount < 1) return nullptr;
-    gamut_hip_sqz_encode_desc d{};
-    d.width = w; d.height = h; d.color_mode = 2; d.levels = 7; d.scan_order = 1; d.subsampling = 1;
-    d.budget = gamut_hip_sqz_budget_from_flags(w, h, flags);
-    if (!img->_device) {
-        int n = 0;
-        uint8_t* r = (uint8_t*)gamut_hip_sqz_write_to_mem(img->_data, (int)img->_pitch, &d, &n);
-        if (r) *len = (size_t)n;
-        return r;
-    }
-    uint8_t* file = (uint8_t*)malloc((size_t)d.budget);               // a host buffer for either writer (gamut_hip_sqz_set_writer): the device writer's file is downloaded into it
-    if (!file) return nullptr;
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
-    if (gamut_hip_sqz_encode_batch_device(&src, &pitch, &d, 1, &off, file, &n, &status, nullptr) != GAMUT_HIP_OK) { free(file); return nullptr; }
-    if (void* shrunk = realloc(file, (size_t)n)) file = (uint8_t*)shrunk;
-    *len = (size_t)n;
-    return file;
-}
-
-uint8_t* gamut_image_save_sqz_to_memory(gamut_image* img, int flags, size_t* len)
-{
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
-    return save_sqz(img, flags, len);
-}
-// saveSQZ with the file left in HBM: device-resident rgb8 images only (a host image has no business there: save_sqz_to_memory)
-uint8_t* gamut_image_save_sqz_to_device(gamut_image* img, int flags, size_t* len)
-{
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data || !img->_device) return nullptr;
-    const int w = img->_width, h = img->_height;
-    if (w < 8 || h < 8 || w > 65535 || h > 65535 || img->_type != GAMUT_PIXEL_rgb8 || img->_layerCount < 1) return nullptr;
-    gamut_hip_sqz_encode_desc d{};
-    d.width = w; d.height = h; d.color_mode = 2; d.levels = 7; d.scan_order = 1; d.subsampling = 1;
-    d.budget = gamut_hip_sqz_budget_from_flags(w, h, flags);
-    if (img->_deviceFile) { (void)hipFree(img->_deviceFile); img->_deviceFile = nullptr; }
-    uint8_t* file = nullptr;
-    if (hipMalloc((void**)&file, (size_t)d.budget) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    const uint8_t* src = img->_data; const int64_t pitch = img->_pitch, off = 0; int64_t n = 0; int status = 0;
-    if (gamut_hip_sqz_encode_batch_to_device(&src, &pitch, &d, 1, &off, file, &n, &status, nullptr) != GAMUT_HIP_OK) { (void)hipFree(file); return nullptr; }
-    img->_deviceFile = file;
-    *len = (size_t)n;
-    return file;
-}
-int gamut_image_save_sqz_to_file(gamut_image* img, const char* path, int flags)
-{
-    if (!path) return 0;
-    size_t n = 0;
-    uint8_t* enc = gamut_image_save_sqz_to_memory(img, flags, &n);
-    if (!enc) return 0;
-    const bool ok = write_file(path, enc, n);
-    free(enc);
-    return ok;
-}
-
-uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len)    // image.d:966-980
-{
-    (void)flags;                                               // saveQOI, saveJPEG and saveGIF ignore them
-    if (len) *len = 0;
-    if (!img || !len || !img->isValid() || !img->_data) return nullptr;
-    if (fif == GAMUT_FORMAT_QOI) return save_qoi(img, len);
-    if (fif == GAMUT_FORMAT_JPEG) return save_jpeg(img, len);
-    if (fif == GAMUT_FORMAT_GIF) return save_gif(img, len);
-    return nullptr;
-}
-int gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags)      // image.d:953-958
-{
-    if (!path) return 0;
-    size_t n = 0;
-    uint8_t* enc = gamut_image_save_to_memory(img, fif, flags, &n);
-    if (!enc) return 0;
-    const bool ok = write_file(path, enc, n);
-    free(enc);
-    return ok;
-}
+// ---- saving: the generic entry (image.d:953-980) and one pair per format that it does not dispatch (savePNG plugins/png.d:172-221, ...) ----
+uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len) { return save_to_memory(generic_saver(fif), img, flags, len); }
+int gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags) { return save_to_file(generic_saver(fif), img, path, flags); }
+uint8_t* gamut_image_save_png_to_memory(gamut_image* img, int flags, size_t* len) { return save_to_memory(save_png, img, flags, len); }
+int gamut_image_save_png_to_file(gamut_image* img, const char* path, int flags) { return save_to_file(save_png, img, path, flags); }
+uint8_t* gamut_image_save_bmp_to_memory(gamut_image* img, int flags, size_t* len) { return save_to_memory(save_bmp, img, flags, len); }
+int gamut_image_save_bmp_to_file(gamut_image* img, const char* path, int flags) { return save_to_file(save_bmp, img, path, flags); }
+uint8_t* gamut_image_save_tga_to_memory(gamut_image* img, int flags, size_t* len) { return save_to_memory(save_tga, img, flags, len); }
+int gamut_image_save_tga_to_file(gamut_image* img, const char* path, int flags) { return save_to_file(save_tga, img, path, flags); }
+uint8_t* gamut_image_save_qoix_to_memory(gamut_image* img, int flags, size_t* len) { return save_to_memory(save_qoix, img, flags, len); }
+int gamut_image_save_qoix_to_file(gamut_image* img, const char* path, int flags) { return save_to_file(save_qoix, img, path, flags); }
+uint8_t* gamut_image_save_dds_to_memory(gamut_image* img, int flags, size_t* len) { return save_to_memory(save_dds, img, flags, len); }
+int gamut_image_save_dds_to_file(gamut_image* img, const char* path, int flags) { return save_to_file(save_dds, img, path, flags); }
+uint8_t* gamut_image_save_sqz_to_memory(gamut_image* img, int flags, size_t* len) { return save_to_memory(save_sqz, img, flags, len); }
+int gamut_image_save_sqz_to_file(gamut_image* img, const char* path, int flags) { return save_to_file(save_sqz, img, path, flags); }
+uint8_t* gamut_image_save_sqz_to_device(gamut_image* img, int flags, size_t* len) { return save_to_memory(save_sqz_to_device, img, flags, len); }
 void gamut_free_encoded_image(void* encoded) { free(encoded); }                          // image.d:32-36
 
 int   gamut_image_type(const gamut_image* img) { return img->_type; }

@@ -181,17 +181,21 @@ class Image:
     def scanptr(self, y): return self.L.gamut_image_scanptr(self.h, y)
     def layerptr(self, layer, y): return self.L.gamut_image_layerptr(self.h, layer, y)
 
-    # saving (image.d:940-1011): QOI and JPEG (layer 0) and GIF (rgba8, every layer a frame), encoded on the GPU
-    def save_to_memory(self, fif, flags=0):
-        """the encoded file as bytes, or None when the image cannot be saved in `fif`"""
+    def _encoded(self, entry, *args):
+        """entry(image, *args, &length), one of the gamut_image_save_*_to_memory functions: its malloc'd file as bytes, freed here, or None"""
         n = _sz(0)
-        p = self.L.gamut_image_save_to_memory(self.h, fif, flags, C.byref(n))
+        p = entry(self.h, *args, C.byref(n))
         if not p:
             return None
         try:
             return C.string_at(p, n.value)
         finally:
             self.L.gamut_free_encoded_image(p)
+
+    # saving (image.d:940-1011): QOI and JPEG (layer 0) and GIF (rgba8, every layer a frame), encoded on the GPU
+    def save_to_memory(self, fif, flags=0):
+        """the encoded file as bytes, or None when the image cannot be saved in `fif`"""
+        return self._encoded(self.L.gamut_image_save_to_memory, fif, flags)
     saveToMemory = save_to_memory
 
     def saveToFile(self, fif, path, flags=0): return bool(self.L.gamut_image_save_to_file(self.h, fif, str(path).encode(), flags))
@@ -199,14 +203,7 @@ class Image:
     # savePNG (plugins/png.d:172-221): flags = ENCODE_PNG_COMPRESSION_* | ENCODE_PNG_FILTER_*
     def save_png_to_memory(self, flags=0):
         """the PNG file as bytes, or None when the image's type or the flags are refused"""
-        n = _sz(0)
-        p = self.L.gamut_image_save_png_to_memory(self.h, flags, C.byref(n))
-        if not p:
-            return None
-        try:
-            return C.string_at(p, n.value)
-        finally:
-            self.L.gamut_free_encoded_image(p)
+        return self._encoded(self.L.gamut_image_save_png_to_memory, flags)
     savePNGToMemory = save_png_to_memory
 
     def savePNGToFile(self, path, flags=0): return bool(self.L.gamut_image_save_png_to_file(self.h, str(path).encode(), flags))
@@ -214,14 +211,7 @@ class Image:
     # saveBMP (plugins/bmp.d:166-194): rgb8 / rgba8, 1..32767 pixels each way, one layer
     def save_bmp_to_memory(self, flags=0):
         """the BMP file as bytes, or None when the image is refused"""
-        n = _sz(0)
-        p = self.L.gamut_image_save_bmp_to_memory(self.h, flags, C.byref(n))
-        if not p:
-            return None
-        try:
-            return C.string_at(p, n.value)
-        finally:
-            self.L.gamut_free_encoded_image(p)
+        return self._encoded(self.L.gamut_image_save_bmp_to_memory, flags)
     saveBMPToMemory = save_bmp_to_memory
 
     def saveBMPToFile(self, path, flags=0): return bool(self.L.gamut_image_save_bmp_to_file(self.h, str(path).encode(), flags))
@@ -229,14 +219,7 @@ class Image:
     # saveTGA (plugins/tga.d:128-150): l8 / la8 / rgb8 / rgba8, layer 0, always run-length encoded; flags are ignored
     def save_tga_to_memory(self, flags=0):
         """the TGA file as bytes, or None when the image is refused"""
-        n = _sz(0)
-        p = self.L.gamut_image_save_tga_to_memory(self.h, flags, C.byref(n))
-        if not p:
-            return None
-        try:
-            return C.string_at(p, n.value)
-        finally:
-            self.L.gamut_free_encoded_image(p)
+        return self._encoded(self.L.gamut_image_save_tga_to_memory, flags)
     saveTGAToMemory = save_tga_to_memory
 
     def saveTGAToFile(self, path, flags=0): return bool(self.L.gamut_image_save_tga_to_file(self.h, str(path).encode(), flags))
@@ -244,14 +227,7 @@ class Image:
     # saveQOIX (plugins/qoix.d:156-242): rgb8 / rgba8 / rgbap8, layer 0, LZ4 when that is smaller; flags are ignored
     def save_qoix_to_memory(self, flags=0):
         """the QOIX file as bytes, or None when the image is refused"""
-        n = _sz(0)
-        p = self.L.gamut_image_save_qoix_to_memory(self.h, flags, C.byref(n))
-        if not p:
-            return None
-        try:
-            return C.string_at(p, n.value)
-        finally:
-            self.L.gamut_free_encoded_image(p)
+        return self._encoded(self.L.gamut_image_save_qoix_to_memory, flags)
     saveQOIXToMemory = save_qoix_to_memory
 
     def saveQOIXToFile(self, path, flags=0): return bool(self.L.gamut_image_save_qoix_to_file(self.h, str(path).encode(), flags))
@@ -259,14 +235,7 @@ class Image:
     # saveDDS (plugins/dds.d:47-216): l8 / la8 / rgb8 / rgba8 as BC7 blocks, layer 0; flags are ignored
     def save_dds_to_memory(self, flags=0):
         """the DDS file as bytes, or None when the image is refused"""
-        n = _sz(0)
-        p = self.L.gamut_image_save_dds_to_memory(self.h, flags, C.byref(n))
-        if not p:
-            return None
-        try:
-            return C.string_at(p, n.value)
-        finally:
-            self.L.gamut_free_encoded_image(p)
+        return self._encoded(self.L.gamut_image_save_dds_to_memory, flags)
     saveDDSToMemory = save_dds_to_memory
 
     def saveDDSToFile(self, path, flags=0): return bool(self.L.gamut_image_save_dds_to_file(self.h, str(path).encode(), flags))
@@ -274,14 +243,7 @@ class Image:
     # saveSQZ (plugins/sqz.d:141-201): rgb8 with sides of at least 8, layer 0; Oklab, 7 levels, snake scan; flags = ENCODE_SQZ_QUALITY_*
     def save_sqz_to_memory(self, flags=0):
         """the SQZ file as bytes (the bytes used, at most the budget the flags give), or None when the image is refused"""
-        n = _sz(0)
-        p = self.L.gamut_image_save_sqz_to_memory(self.h, flags, C.byref(n))
-        if not p:
-            return None
-        try:
-            return C.string_at(p, n.value)
-        finally:
-            self.L.gamut_free_encoded_image(p)
+        return self._encoded(self.L.gamut_image_save_sqz_to_memory, flags)
     saveSQZToMemory = save_sqz_to_memory
 
     def save_sqz_to_device(self, flags=0):

@@ -9,8 +9,9 @@
  * LoadFlags / LayoutConstraints bits (types.d:139-348).  Pixel storage is host malloc memory exactly as
  * in the reference (the user may disown and free() it); every pixel operation (decode, convertTo) runs
  * on the GPU through gamut_hip_* -- there is no CPU pixel path.
- * Formats: JPEG (baseline), PNG, QOI, BMP and GIF (every frame a layer of an rgba8 image) are read; QOI, JPEG and GIF are written (saveToMemory / saveToFile), PNG and BMP through their own entries; other signatures report
- * "Unidentified image format".
+ * Formats read: JPEG (baseline), PNG, QOI, QOIX (the 8-bit colour files), BMP, TGA, SQZ and GIF (every frame a layer of an rgba8
+ * image); anything else reports "Unidentified image format".  Formats written: QOI, JPEG and GIF through the generic entries
+ * (saveToMemory / saveToFile); PNG, BMP, TGA, QOIX, DDS (written only, never read) and SQZ each through a pair of entries of its own.
  */
 #ifndef GAMUT_IMAGE_H
 #define GAMUT_IMAGE_H
@@ -127,10 +128,10 @@ int gamut_image_copy_pixels_to_host(gamut_image* img, int layer, void* dst, int6
  * stbi_write_jpg_to_func writes): l8 (one component) / rgb8 (three), quality 90, so 4:2:0; rgba8 and every other type are refused
  * as saveJPEG refuses them.  GIF (gamut_hip_gif_encode*, byte for byte what saveGIF, plugins/gif.d:105-147, writes): rgba8 only, and
  * unlike the other two EVERY layer is encoded, as a frame of 7 centiseconds (any layer count >= 1; upside-down and padded layouts are
- * honoured).  GAMUT_FORMAT_PNG is not dispatched from these two generic entries yet (they return NULL / 0 for it, as
- * for an errored image or an unknown format): PNG is saved through gamut_image_save_png_to_memory / _to_file below.  Neither is
- * GAMUT_FORMAT_BMP (7): BMP is saved through gamut_image_save_bmp_to_memory / _to_file below.  Flags are
- * ignored here (as the three plugins do).  The image's state and error are left as they were. */
+ * honoured).  These two generic entries dispatch those three formats only: for GAMUT_FORMAT_PNG, _BMP, _TGA, _QOIX, _DDS and _SQZ
+ * they return NULL / 0, as for an errored image or an unknown format, and each of the six is saved through its own
+ * gamut_image_save_<format>_to_memory / _to_file pair below.  Flags are ignored here (as the three plugins do; of all the savers
+ * only PNG and SQZ read theirs).  The image's state and error are left as they were. */
 uint8_t* gamut_image_save_to_memory(gamut_image* img, int fif, int flags, size_t* len);   /* image.d:966-980; NULL (and *len = 0) on refusal */
 int      gamut_image_save_to_file(gamut_image* img, int fif, const char* path, int flags); /* image.d:953-958; 1 on success */
 void     gamut_free_encoded_image(void* encoded);                                       /* image.d:32-36 */
