@@ -208,6 +208,15 @@ extern(C)
                                             gamut_hip_sqz_info* info, int* status_host, void* stream);
     const(ubyte)* gamut_hip_sqz_linear_to_srgb_table();
     float gamut_hip_sqz_last_decode_stage_ms(int stage);
+    // SQZ read on the device: the front end as HIP kernels, one workgroup per file; files in host memory -> coefficients in device memory,
+    // value for value those of decode_coeffs.  set_reader(0 host / 1 device) chooses what decode_batch_device and the Image layer run; it
+    // returns the previous value.
+    int   gamut_hip_sqz_read_batch_device(const(ubyte*)* data, const(size_t)* len, int count, short* coeffs, const(long)* coeff_offset,
+                                          gamut_hip_sqz_info* info, int* status_host, void* stream);
+    int   gamut_hip_sqz_set_reader(int which);
+    int   gamut_hip_sqz_read_window();
+    long  gamut_hip_sqz_set_read_chunk(long coefficients);
+    float gamut_hip_sqz_last_read_stage_ms(int stage);
     // SQZ encode (SQZ_encode codecs/sqz.d:2208-2240, saveSQZ plugins/sqz.d:141-201).  analyze_batch_device is the front half on the GPU (colour
     // transform, DWT, sign-magnitude: the coefficient buffer reconstruct_batch_device consumes), dwt_batch_device the same fed with int16
     // planes, encode_coeffs the bit-plane writer on the host, encode_batch_device both: device pixels -> files in HOST memory.

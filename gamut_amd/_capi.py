@@ -207,6 +207,11 @@ SIGNATURES = {
     "gamut_hip_sqz_write_chunk": (_i, []),
     "gamut_hip_sqz_last_write_stage_ms": (_f, [_i]),
     "gamut_hip_sqz_set_writer": (_i, [_i]),
+    "gamut_hip_sqz_read_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_sz), _i, _vp, C.POINTER(_i64), C.POINTER(SqzInfo), _pi, _vp]),
+    "gamut_hip_sqz_set_reader": (_i, [_i]),
+    "gamut_hip_sqz_read_window": (_i, []),
+    "gamut_hip_sqz_set_read_chunk": (_i64, [_i64]),
+    "gamut_hip_sqz_last_read_stage_ms": (_f, [_i]),
     "gamut_hip_flip_device": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
     "gamut_hip_flip": (_i, [_i, _vp, _i, _i, _i, _i]),
     "gamut_hip_jpeg_read_header": (_i, [_vp, _sz, C.POINTER(JpegFrame)]),

@@ -1,6 +1,6 @@
 // sqz.hip -- the SQZ back end on the GPU and the two batch calls: coefficient planes in HBM -> l8 / rgb8 pixels, bit for bit what
 // SQZ_dwt_convert_from_sign_magnitude, SQZ_idwt and SQZ_color_process (source/gamut/codecs/sqz.d:1584-1592, 1699-1796, 1153-1546)
-// make of them.  The front end (the bit stream) is sqz_host.hip.
+// make of them.  The front end (the bit stream) is sqz_host.hip on host threads or sqz_read.hip on the device, by gamut_hip_sqz_set_reader.
 //
 // THE REFERENCE'S ORDER, AND WHY A LEVEL IS DATA-PARALLEL.  SQZ_idwt_5_3i (:1743-1770) walks a level's rows in pairs: the vertical
 // lifting of an even row r (r -= (n + s + 2) >> 2, n and s the odd rows around it), then of the odd row n above it (n += (nn + r) >> 1,
@@ -32,6 +32,9 @@ bool sqz_valid_geometry(int64_t w, int64_t h, int mode, int scan, int levels);  
 int  sqz_parse_header(const uint8_t* data, size_t len, gamut_hip_sqz_info* info);
 int  sqz_decode_coeffs(const uint8_t* data, size_t len, int16_t* out, size_t capacity, gamut_hip_sqz_info* info);
 const uint8_t* sqz_linear_to_srgb_table();
+int  sqz_reader();                                                  // sqz_read.hip: 0 the host front end, 1 the device reader
+int  sqz_read_files(const uint8_t* const* data, const size_t* len, const gamut_hip_sqz_info* info, const std::vector<int>& which,
+                    int16_t* coeffs, const int64_t* coeff_offset, hipStream_t stream);
 namespace {
 
 constexpr int kThreads = 256, kTW = 128, kTH = 16, kRows = kTH + 3, kNL = kTW / 2 + 1, kNH = kTW / 2 + 2;
@@ -323,6 +326,16 @@ int decode_batch(const uint8_t* const* data, const size_t* len, int count, const
         static thread_local PerDevice<DeviceScratch> coeff_pd;
         static thread_local PerDevice<PinnedScratch> stage_pd;
         int16_t* dco = (int16_t*)coeff_pd.cur().get(bytes, stream);
+        if (sqz_reader() == 1) {                                    // the device reader: files up, no coefficient crosses the bus
+            if (!dco) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_decode: %zu coefficient bytes could not be had", bytes);
+            std::vector<int64_t> coff((size_t)count, 0);
+            for (int i : good) coff[(size_t)i] = descs[(size_t)i].coeff_offset;
+            if (timing) t_stage_ms[1] = t_stage_ms[2] = -1.0f;
+            if (int rc = sqz_read_files(data, len, hd.data(), good, dco, coff.data(), stream)) return rc;
+            if (int rc = reconstruct(dco, descs.data(), out_offset, good, out, stream)) return rc;
+            if (first_bad >= 0) return set_error(first_rc, "image %d: %s", first_bad, first_msg);
+            return GAMUT_HIP_OK;
+        }
         int16_t* hco = (int16_t*)stage_pd.cur().get(bytes, stream);
         if (!dco || !hco) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_decode: staging of %zu coefficient bytes failed", bytes);
         // the front end: one file per host thread, straight into the pinned staging

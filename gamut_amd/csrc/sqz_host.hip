@@ -3,8 +3,10 @@
 // the coefficient buffer the GPU's front half (sqz_encode.hip) leaves.  Host code only: no device is needed or touched.
 //
 // SQZ is an embedded bit-plane coder (WDR: wavelet difference reduction): ONE bit stream, three linked lists per subband (LIP
-// insignificant, NSP newly significant, LSP significant) and a scheduler that interleaves the subbands round by round.  Nothing in
-// it is parallel inside a file; the batch call (sqz.hip) runs one file per host thread.  What leaves this file is the reference's
+// insignificant, NSP newly significant, LSP significant) and a scheduler that interleaves the subbands round by round.  The chain
+// of (band, bit plane) segments is serial -- where one ends is known only once it has been read -- so this file walks a file bit by
+// bit and the batch call (sqz.hip) runs one file per host thread; INSIDE a segment every bit position can be classified without its
+// neighbours, which is what the device reader (sqz_read.hip, sqz_read.hpp) is built on.  What leaves this file is the reference's
 // coefficient buffer as it stands before SQZ_dwt_convert_from_sign_magnitude: int16 sign-magnitude values (bit 0 the sign), planes
 // one after another, subbands interleaved in place (SQZ_common_init_context :1798-1829).
 //

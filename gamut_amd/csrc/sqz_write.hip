@@ -49,8 +49,6 @@
 // A budget above 2^56 bytes counts as 2^56 (8 * budget must fit 64 bits).
 #include "sqz_write.hpp"
 #include <climits>
-#include <map>
-#include <tuple>
 
 namespace gamut {
 namespace {
@@ -60,7 +58,6 @@ constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr uint64_t kNone = ~0ull;
 constexpr uint64_t kChunkCoeffs = 1ull << 29;
 constexpr size_t kChunkImages = 4096;
-constexpr size_t kTableCap = 1ull << 30;
 constexpr int kGatherY = 32, kPlaceX = 64;
 
 struct WBand { const uint32_t* table; int64_t coeff_base; uint64_t comp_base; uint32_t n, bw, stride; int32_t round; };     // n == 0: an empty slot
@@ -347,33 +344,6 @@ thread_local float t_write_ms[2] = { -1.0f, -1.0f };
 struct Writer {
     DeviceScratch blob, comp, lsp, files;
     PinnedScratch pinned, staged;
-    std::map<std::tuple<int, uint32_t, uint32_t>, uint32_t*> tables;
-    size_t table_bytes = 0;
-
-    void drop_tables()
-    {
-        for (auto& t : tables) (void)hipFree(t.second);
-        tables.clear(); table_bytes = 0;
-    }
-    // the (x, y) table of a band in DEVICE memory; NULL with the thread's message when it cannot be had
-    const uint32_t* table(int order, uint32_t w, uint32_t h)
-    {
-        const auto key = std::make_tuple(order, w, h);
-        const auto it = tables.find(key);
-        if (it != tables.end()) return it->second;
-        const size_t n = (size_t)w * h;
-        std::vector<uint32_t> xy(n);                                // an (x, y) pair of uint16 is x | y << 16
-        if (sqz_scan_order(order, (int)w, (int)h, reinterpret_cast<uint16_t*>(xy.data())) != GAMUT_HIP_OK) return nullptr;
-        uint32_t* d = nullptr;
-        if (hipMalloc((void**)&d, n * 4) != hipSuccess || hipMemcpy(d, xy.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            if (d) (void)hipFree(d);
-            set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz_write: a scan table of %zu bytes could not be had", n * 4);
-            return nullptr;
-        }
-        tables[key] = d; table_bytes += n * 4;
-        return d;
-    }
 };
 
 struct Job {
@@ -381,7 +351,7 @@ struct Job {
     const int64_t* out_offset; uint8_t* out; bool out_on_device; int64_t* out_len; int* rcs; hipStream_t stream; bool timing;
 };
 
-int write_chunk(Writer& W, const Job& J, size_t a, size_t b)
+int write_chunk(Writer& W, SqzScanTables& T, const Job& J, size_t a, size_t b)
 {
     const size_t n = b - a, nb = n * kSqzSlots;
     hipStream_t stream = J.stream;
@@ -409,7 +379,7 @@ int write_chunk(Writer& W, const Job& J, size_t a, size_t b)
             B.n = g[s].width * g[s].height; B.bw = g[s].width; B.stride = g[s].stride;
             B.coeff_base = J.coeff_offset[i] + g[s].offset; B.comp_base = elems;
             elems += B.n;
-            if (D.scan_order != 0 && !(B.table = W.table(D.scan_order, g[s].width, g[s].height))) return GAMUT_HIP_ERR_OUT_OF_MEMORY;
+            if (D.scan_order != 0 && !(B.table = T.table(D.scan_order, g[s].width, g[s].height))) return GAMUT_HIP_ERR_OUT_OF_MEMORY;
         }
         const uint64_t budget = (uint64_t)std::min<int64_t>(D.budget, (int64_t)1 << 56);
         hi[k].limit = budget * 8u;
@@ -490,6 +460,35 @@ int write_chunk(Writer& W, const Job& J, size_t a, size_t b)
 
 } // namespace
 
+void SqzScanTables::drop_tables()
+{
+    for (auto& t : tables) (void)hipFree(t.second);
+    tables.clear(); table_bytes = 0;
+}
+const uint32_t* SqzScanTables::table(int order, uint32_t w, uint32_t h)
+{
+    const auto key = std::make_tuple(order, w, h);
+    const auto it = tables.find(key);
+    if (it != tables.end()) return it->second;
+    const size_t n = (size_t)w * h;
+    std::vector<uint32_t> xy(n);                                    // an (x, y) pair of uint16 is x | y << 16
+    if (sqz_scan_order(order, (int)w, (int)h, reinterpret_cast<uint16_t*>(xy.data())) != GAMUT_HIP_OK) return nullptr;
+    uint32_t* d = nullptr;
+    if (hipMalloc((void**)&d, n * 4) != hipSuccess || hipMemcpy(d, xy.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "sqz: a scan table of %zu bytes could not be had", n * 4);
+        return nullptr;
+    }
+    tables[key] = d; table_bytes += n * 4;
+    return d;
+}
+SqzScanTables& sqz_scan_tables()
+{
+    static thread_local PerDevice<SqzScanTables> pd;
+    return pd.cur();
+}
+
 int sqz_write_files(const int16_t* coeffs, const int64_t* coeff_offset, const gamut_hip_sqz_encode_desc* descs, const std::vector<int>& which,
                     const int64_t* out_offset, uint8_t* out, bool out_on_device, int64_t* out_len, std::vector<int>& rcs, hipStream_t stream)
 {
@@ -498,7 +497,8 @@ int sqz_write_files(const int16_t* coeffs, const int64_t* coeff_offset, const ga
     rcs.assign(which.size(), GAMUT_HIP_OK);
     if (which.empty()) return GAMUT_HIP_OK;
     Writer& W = writer_pd.cur();
-    if (W.table_bytes > kTableCap) W.drop_tables();                 // (every call ends with a wait on its stream: nothing reads them now)
+    SqzScanTables& T = sqz_scan_tables();
+    if (T.table_bytes > kSqzTableCap) T.drop_tables();                 // (every call ends with a wait on its stream: nothing reads them now)
     if (timing) t_write_ms[0] = t_write_ms[1] = 0.0f;
     const Job J{ coeffs, coeff_offset, descs, which.data(), out_offset, out, out_on_device, out_len, rcs.data(), stream, timing };
     for (size_t a = 0; a < which.size(); ) {
@@ -509,7 +509,7 @@ int sqz_write_files(const int16_t* coeffs, const int64_t* coeff_offset, const ga
             if (b > a && elems + e > kChunkCoeffs) break;
             elems += e; ++b;
         }
-        if (int rc = write_chunk(W, J, a, b)) return rc;
+        if (int rc = write_chunk(W, T, J, a, b)) return rc;
         a = b;
     }
     return GAMUT_HIP_OK;

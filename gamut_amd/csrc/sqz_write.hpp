@@ -2,6 +2,8 @@
 // (sqz_write.hip) and the batch calls above both writers (sqz_encode.hip).
 #pragma once
 #include "common.hpp"
+#include <map>
+#include <tuple>
 
 namespace gamut {
 
@@ -16,6 +18,19 @@ int  sqz_scan_order(int order, int width, int height, uint16_t* xy);
 int  sqz_encode_check(gamut_hip_sqz_encode_desc* d);
 int  sqz_encode_coeffs(const int16_t* planes, const gamut_hip_sqz_encode_desc& d, uint8_t* dst, int64_t* len);
 int  sqz_undefined_shift_error();                                   // deviation (1): sets the message, returns GAMUT_HIP_ERR_INVALID_ARG
+
+// The (x, y) tables of the bands' scans in DEVICE memory, x | y << 16 per position: what the device writer gathers through and the
+// device reader (sqz_read.hip) fills its lists from.  Kept per thread and device, one per distinct (order, band width, band height),
+// 4 bytes per coefficient of the band; a call that finds more than 1 GiB of them drops them all before it builds what it needs
+// (every call ends with a wait on its stream, so nothing reads them then).
+struct SqzScanTables {
+    std::map<std::tuple<int, uint32_t, uint32_t>, uint32_t*> tables;
+    size_t table_bytes = 0;
+    void drop_tables();
+    const uint32_t* table(int order, uint32_t w, uint32_t h);       // NULL with the thread's message when it cannot be had
+};
+SqzScanTables& sqz_scan_tables();                                   // the calling thread's, on the current device
+constexpr size_t kSqzTableCap = 1ull << 30;
 
 // The lowest-numbered refused image of a batch call, with the message it was refused with
 struct SqzRefusals {

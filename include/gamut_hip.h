@@ -659,6 +659,33 @@ const uint8_t* gamut_hip_sqz_linear_to_srgb_table(void);
  * upload (wall clock until the upload is queued); -1 when timing is off, nothing was decoded or `stage` is out of range */
 float gamut_hip_sqz_last_decode_stage_ms(int stage);
 
+/* ---- SQZ read on the device (SQZ_schedule_task's read side, codecs/sqz.d:1941-2168, as HIP kernels) ------------------------------
+ * The front end again, without the host threads: one workgroup per file walks the chain of (band, bit plane) segments and spends all
+ * its lanes inside each -- flags by parity, records ranked and their advances summed by workgroup prefix sums, the first run past the
+ * list found by a minimum (gamut_amd/csrc/sqz_read.hip; the rules by bit position are in sqz_read.hpp).  The files are in HOST
+ * memory and go up through pinned staging; file i's planes * width * height int16 coefficients land in DEVICE memory at coeffs +
+ * coeff_offset[i] (int16 elements, >= 0), value for value what gamut_hip_sqz_decode_coeffs writes -- the buffer behind
+ * SQZ_decode_round_coefficients, ready for gamut_hip_sqz_reconstruct_batch_device.  data, len, coeff_offset, info and status_host
+ * are host arrays; info and status_host may be NULL.  The header's refusals are the host's: a refused file (or a negative
+ * coeff_offset[i]) writes nothing, its neighbours are read, and the call returns the status of the lowest-numbered refused file
+ * ("image %d: ...").  Nothing outside a file's own coefficients is written.  Returns when they are in place. */
+int gamut_hip_sqz_read_batch_device(const uint8_t* const* data, const size_t* len, int count, int16_t* coeffs, const int64_t* coeff_offset,
+                                    gamut_hip_sqz_info* info, int* status_host, void* stream);
+/* Which front end gamut_hip_sqz_decode_batch_device and the Image layer's SQZ load run behind their unchanged signatures: 0 the host
+ * front end, 1 the device reader (no coefficient crosses the bus; gamut_hip_sqz_last_decode_stage_ms then gives -1 for stages 1 and
+ * 2).  Returns the previous value; any other argument changes nothing.  Process-wide; the initial value is
+ * GAMUT_HIP_SQZ_READER=host|device from the environment, default host. */
+int gamut_hip_sqz_set_reader(int which);
+/* the bits of a sorting pass the device reader's workgroup takes per step (tests size their cases around it) */
+int gamut_hip_sqz_read_window(void);
+/* The device reader takes a batch in chunks of files that have at most this many coefficients between them (its lists are 8 bytes
+ * per coefficient; one larger file is a chunk of its own).  Sets the limit and returns the previous one; a value below 1 changes
+ * nothing.  Process-wide. */
+int64_t gamut_hip_sqz_set_read_chunk(int64_t coefficients);
+/* measurements, under GAMUT_HIP_SQZ_TIMING=1: milliseconds of the calling thread's last call that ran the device reader -- 0: its
+ * kernels (GPU time, all chunks), 1: building the band tables, staging the files and queueing the upload (wall clock); -1 otherwise */
+float gamut_hip_sqz_last_read_stage_ms(int stage);
+
 /* ---- SQZ encode (SQZ_encode, codecs/sqz.d:2208-2240; saveSQZ, plugins/sqz.d:141-201) -----------------------------------------------
  * The decoder's split, mirrored.  The FRONT HALF (HIP kernels, gamut_hip_sqz_analyze_batch_device) is SQZ_color_process(read = 1) for
  * the four colour modes, SQZ_dwt (the in-place 5/3 integer DWT, one launch per level over the whole batch) and
