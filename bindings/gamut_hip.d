@@ -276,6 +276,12 @@ extern(C)
     int   gamut_hip_qoix_row_capacity();
     float gamut_hip_qoix_last_decode_kernel_ms();
     float gamut_hip_qoix_last_decode_stage_ms(int stage);
+    // QOI-Plane (8-bit files with 1 or 2 channels, codecs/qoiplane.d:377-541) behind a process-wide switch: set_plane(0 | 1) returns the
+    // previous value (any other argument changes nothing); the initial value is GAMUT_HIP_QOIX_PLANE=0|1, default 0 (such files are
+    // GAMUT_HIP_ERR_UNSUPPORTED).  On: l8 / la8 decode, channels 1 / 2 accepted for grey files.
+    int   gamut_hip_qoix_set_plane(int on);
+    int   gamut_hip_qoix_plane_row_capacity();
+    float gamut_hip_qoix_last_plane_kernel_ms();
     // QOIX encode: qoix_lz4_encode as saveQOIX drives it for 8-bit rgb / rgba (plugins/qoix.d:156-339, codecs/qoi2avg.d:376-615,
     // codecs/lz4.d:289-554), byte for byte.  mode 0: LZ4 when lz4Size + 4 < datalen, 1: always stored.  Deviations: width * channels bytes
     // of a row are read whatever the pitch is; a bound above 2^31 - 1 is refused.

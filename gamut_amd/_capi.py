@@ -177,6 +177,9 @@ SIGNATURES = {
     "gamut_hip_qoix_row_capacity": (_i, []),
     "gamut_hip_qoix_last_decode_kernel_ms": (_f, []),
     "gamut_hip_qoix_last_decode_stage_ms": (_f, [_i]),
+    "gamut_hip_qoix_set_plane": (_i, [_i]),
+    "gamut_hip_qoix_plane_row_capacity": (_i, []),
+    "gamut_hip_qoix_last_plane_kernel_ms": (_f, []),
     "gamut_hip_qoix_encode_bound": (_i64, [C.POINTER(QoixDesc)]),
     "gamut_hip_qoix_encode_batch_device": (_i, [C.POINTER(_vp), C.POINTER(_i64), C.POINTER(QoixDesc), _i, C.POINTER(_i64), _vp,
                                             C.POINTER(_i64), _pi, _vp]),

@@ -446,7 +446,8 @@ struct gamut_image {
         const int requested = computeRequestedImageComponents(flags);                       // :92-99: only its verdict is used
         if (requested == 0) { error(kStrInvalidFlags); return; }
         gamut_hip_qoix_info hd, info;
-        // qoix_lz4_decode :112: the flags are only validated, decodedType = streamType; a sub-codec that is not built yet fails the same way
+        // qoix_lz4_decode :112: the flags are only validated, decodedType = streamType; a sub-codec that is not built (10-bit) or not
+        // switched on (8-bit grey, gamut_hip_qoix_set_plane) fails the same way.  Switched on, l8 / la8 files take this path unchanged.
         if (!validLoadFlags(flags) || gamut_hip_qoix_read_header(bytes, len, &hd) != GAMUT_HIP_OK) { error(kStrImageDecodingFailed); return; }
         const int comps = hd.channels;
         uint8_t* decoded = decodeOne((size_t)hd.width * hd.height * comps, [&](uint8_t* dev, const int64_t* zero, int* st) {

@@ -3,7 +3,8 @@
 // (source/gamut/codecs/qoi2avg.d:624-897), many files per call.  The header is read on the host (qoix_host.hip).
 //
 // The files of a batch go up in one blob through pinned staging, each at a 16-byte boundary with zero bytes behind it; positions
-// >= the file's length are never loaded.  Two launches, whatever the batch holds:
+// >= the file's length are never loaded.  Two launches, whatever a batch of colour files holds (grey files, behind
+// gamut_hip_qoix_set_plane, add a third: k_qoix_plane, described where it stands):
 //
 // k_qoix_lz4 -- a wave per compressed file.  The sequence walk (token, length extensions, offset) is wave-uniform and reads its
 // bytes from a 512-byte window of the file that the lanes hold a dword each (v_readlane); literal runs and matches are copied by
@@ -40,6 +41,7 @@ extern "C" int gamut_valid_load_flags(int flags);                              /
 namespace gamut {
 int qoix_parse_header(const uint8_t* data, size_t len, gamut_hip_qoix_info* info, uint32_t* sub_size);       // qoix_host.hip
 int qoix_fail(const char* why);
+bool qoix_plane_on();
 namespace {
 
 constexpr int kWave = 64;
@@ -57,7 +59,7 @@ struct QxImg {                                                                 /
     uint32_t* wide_row;                                                        // w + 8 dwords of global scratch when w > kRowCap
     int64_t  out_off;
     uint32_t avail, w, h, status;                                              // avail: qoix_decode's `size`
-    uint32_t outc, pad;
+    uint32_t outc, plane;                                                      // plane: a QOI-Plane stream (k_qoix_plane), else QOI2AVG
 };
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
@@ -73,14 +75,23 @@ template <class Rec> struct ByteWindow {
         cur = file_dword(r, 256ull * chunk + 4u * lane);
         nxt = file_dword(r, 256ull * chunk + 256u + 4u * lane);
     }
-    __device__ __forceinline__ uint32_t byte(const Rec& r, uint32_t pos, uint32_t lane)                 // pos: uniform
+    __device__ __forceinline__ void seek(const Rec& r, uint32_t c, uint32_t lane)                       // c: uniform, the chunk `cur` is to hold
     {
-        const uint32_t c = pos >> 8;
         if (c != idx) {
             if (c == idx + 1) { cur = nxt; idx = c; nxt = file_dword(r, 256ull * c + 256u + 4u * lane); }
             else load(r, c, lane);
         }
+    }
+    __device__ __forceinline__ uint32_t byte(const Rec& r, uint32_t pos, uint32_t lane)                 // pos: uniform
+    {
+        seek(r, pos >> 8, lane);
         return ((uint32_t)__builtin_amdgcn_readlane((int)cur, (int)((pos >> 2) & 63u)) >> (8u * (pos & 3u))) & 255u;
+    }
+    // dword d (0..127, its own per lane) of the 512 bytes held: one ds_bpermute from each half
+    __device__ __forceinline__ uint32_t dword(uint32_t d) const
+    {
+        const uint32_t a = __shfl(cur, (int)(d & 63u)), b = __shfl(nxt, (int)(d & 63u));
+        return d < 64u ? a : b;
     }
 };
 
@@ -268,9 +279,175 @@ __global__ void __launch_bounds__(kWave) k_qoix_avg(const QxImg* __restrict__ im
     if (!ok && lane == 0) atomicOr(&status[im.status], 2u);
 }
 
-// Measurements (tools/qoix_bench.py): with GAMUT_HIP_QOIX_TIMING=1 the decode call brackets each of its two kernels -- not the upload --
-// with events and keeps the GPU times of the calling thread's last call; the blob is resident in HBM when the first event is reached.
-thread_local float t_last_ms[2] = { -1.0f, -1.0f };
+// ---- QOI-Plane: qoiplane_decode (source/gamut/codecs/qoiplane.d:377-541), 8-bit luminance or luminance + alpha, behind
+// gamut_hip_qoix_set_plane.  Ops sit on nibble boundaries; with first nibble n0 (and the one behind it, n1):
+//   0..7 DIFF1 (1 nibble)   8,9 DIFF2 (2)   a DIRECT (3)   b n1>0 ADIFF (2)   b 0 LA (6)   c..e REPEAT1 (1)   f REPEAT2 (3)
+// Neither an op's length nor its pixel count (ADIFF 0, REPEAT1 1 + (n0 & 3), REPEAT2 byte + 4 or "to the end" for byte 255, else 1)
+// depends on a pixel value, so a wave takes the stream 64 nibbles at a time and the lanes parse:
+//   * every lane holds the nibble at np + lane and the 5 behind it (ByteWindow fetches 256 bytes ahead; two ds_bpermute pairs);
+//   * op starts: lane i's nibble maps "the next op starts o nibbles on" (o = 0..5) to o - 1, or to length - 1 for o = 0; the six
+//     results are six bytes, composing two such maps is two v_perm_b32, and a 6-step scan over the lanes gives every lane the offset
+//     it is entered with.  A group begins at an op start (np moves by 64 + the offset the last lane leaves), so the entry offset
+//     carried between groups is always 0 and the scan is the pointer-doubling over the ops;
+//   * pixel index: a prefix sum of the counts, saturating at the pixels still missing; an op at or past that point is surplus;
+//   * alpha changes at LA (absolute) and by the LAST ADIFF in front of a pixel op (previous pixel's alpha + d - 8): a segmented
+//     prefix sum over the lanes, (set, value) pairs;
+//   * luminance: DIRECT / LA absolute, REPEAT the left pixel, DIFF (top + left + 1) / 2 + d.  Only this is a chain: a wave-uniform
+//     loop over the group's pixel ops on scalar values.  `top` was fetched by the lanes before the loop (the row buffer holds the
+//     pixel above until the pixel below replaces it); when the row is narrower than the group's pixels, top was produced inside
+//     this group and is looked up among the lanes' results (a ballot and a v_readlane);
+//   * the pixels go to ONE row in the OUTPUT's layout (1 or 2 bytes a pixel: `top` is channel 0 of the pixel above, as in the
+//     reference, which reads it from its output) -- kPlaneCap pixels of LDS, 8 KiB a wave as k_qoix_avg, or a global scratch row --
+//     single pixels by their lanes, runs 64 pixels a step; a finished row leaves through flush_run.
+// Every group consumes at least one nibble, the walk ends at width * height.
+// DEVIATION P1: an op of which a nibble lies at byte index >= size refuses the file (the reference has no input bound; the four closing
+// bytes ARE decoded: f ff is "repeat to the end", which is how a stream ends).
+constexpr uint32_t kPlaneCap = 4096;
+enum : uint32_t { kPDiff = 0, kPAbs = 1, kPRep = 2, kPAdiff = 3 };
+
+template <bool kWide> __device__ __forceinline__ bool plane_decode(const QxImg& im, uint32_t* row, uint8_t* out, uint32_t lane)
+{
+    const uint32_t w = im.w, outc = im.outc, total = w * im.h;                 // (< 400000000)
+    const uint64_t nib_end = 2ull * im.avail;
+    uint8_t* dst = out + im.out_off;
+    uint8_t* rowb = reinterpret_cast<uint8_t*>(row);
+    auto store = [&](uint32_t pos, uint32_t v) {
+        if (outc == 1) rowb[pos] = (uint8_t)v; else reinterpret_cast<uint16_t*>(rowb)[pos] = (uint16_t)v;
+    };
+    ByteWindow<QxImg> win; win.load(im, 0, lane);
+    uint64_t np = 2ull * kHeader;                                              // nibble index of the group's first op
+    uint32_t done = 0, x = 0, y = 0, l = 0, a = 255, pend = 0;                 // pend: 0x100 | d of an ADIFF that ended the previous group
+    while (done < total) {
+        if (np >= nib_end) return false;                                       // DEVIATION P1
+        wave_order();
+        // the nibbles np + lane .. np + lane + 5
+        const uint64_t q = np + lane;
+        const uint32_t bp = (uint32_t)(q >> 1);
+        win.seek(im, (uint32_t)(np >> 9), lane);
+        const uint32_t dw = (bp >> 2) - 64u * win.idx;                         // 0..72
+        const uint32_t raw = __builtin_amdgcn_alignbyte(win.dword(dw + 1), win.dword(dw), bp & 3u);      // bytes bp .. bp + 3
+        const uint32_t nb = __builtin_bswap32(raw) << (4u * ((uint32_t)q & 1u));
+        const uint32_t n0 = nb >> 28, n1 = (nb >> 24) & 15u, n2 = (nb >> 20) & 15u, n3 = (nb >> 16) & 15u, n45 = (nb >> 8) & 255u;
+        const uint32_t len = n0 < 8u ? 1u : n0 < 10u ? 2u : n0 == 10u ? 3u : n0 == 11u ? (n1 ? 2u : 6u) : n0 == 15u ? 3u : 1u;
+        // op starts
+        uint32_t tlo = 0x02010000u | (len - 1u), thi = 0x00000403u;
+        #pragma unroll
+        for (uint32_t d = 1; d < kWave; d <<= 1) {
+            const uint32_t olo = __shfl_up(tlo, d), ohi = __shfl_up(thi, d);
+            if (lane >= d) {
+                const uint32_t nlo = __builtin_amdgcn_perm(thi, tlo, olo), nhi = __builtin_amdgcn_perm(thi, tlo, ohi);
+                tlo = nlo; thi = nhi;
+            }
+        }
+        const uint32_t entered = __shfl_up(tlo, 1u) & 255u;
+        const bool start = lane == 0 || entered == 0;
+        const uint32_t leaves = (uint32_t)__builtin_amdgcn_readlane((int)tlo, 63) & 255u;
+        // what the op does
+        const uint32_t rem = total - done;
+        uint32_t type, val = 0, cnt = 1;
+        if (n0 < 8u) { type = kPDiff; val = n0 - 4u; }
+        else if (n0 < 10u) { type = kPDiff; val = ((n0 & 1u) << 4 | n1) - 16u; }
+        else if (n0 == 10u) { type = kPAbs; val = n1 << 4 | n2; }
+        else if (n0 == 11u) { if (n1) { type = kPAdiff; cnt = 0; } else { type = kPAbs; val = n2 << 4 | n3; } }
+        else if (n0 < 15u) { type = kPRep; cnt = 1u + (n0 & 3u); }
+        else { type = kPRep; const uint32_t b = n1 << 4 | n2; cnt = b == 255u ? rem : b + 4u; }
+        const bool is_la = n0 == 11u && n1 == 0;
+        cnt = start ? min(cnt, rem) : 0u;
+        uint32_t sum = cnt;                                                    // inclusive, saturating at rem
+        #pragma unroll
+        for (uint32_t d = 1; d < kWave; d <<= 1) {
+            const uint32_t o = __shfl_up(sum, d);
+            if (lane >= d) sum = min(sum + o, rem);
+        }
+        const uint32_t before = __shfl_up(sum, 1u);
+        const uint32_t pix = lane ? before : 0u;                               // pixels of this group in front of the op
+        const uint32_t group = (uint32_t)__builtin_amdgcn_readlane((int)sum, 63);
+        const bool live = start && pix < rem;                                  // else surplus: never read
+        if (__ballot(live && ((q + len - 1u) >> 1) >= im.avail)) return false; // DEVIATION P1
+        cnt = min(cnt, rem - min(pix, rem));
+        const bool pixop = live && type != kPAdiff;
+        // alpha: (set << 8 | value) pairs; the last ADIFF in front of a pixel op adds d - 8 to the previous pixel's alpha
+        const uint64_t lives = __ballot(live), below = lives & ((1ull << lane) - 1ull);
+        const uint32_t adw = type == kPAdiff ? 0x100u | n1 : 0u;
+        const uint32_t prev = __shfl(adw, below ? 63 - __builtin_clzll(below) : 0);
+        const uint32_t front = below ? prev : pend;
+        uint32_t av = 0;
+        if (pixop) av = is_la ? 0x100u | n45 : (front & 0x100u) ? ((front & 15u) - 8u) & 255u : 0u;
+        #pragma unroll
+        for (uint32_t d = 1; d < kWave; d <<= 1) {
+            const uint32_t o = __shfl_up(av, d);
+            if (lane >= d && !(av & 0x100u)) av = (o & 0x100u) | ((o + av) & 255u);
+        }
+        const uint32_t ares = (av & 0x100u) ? av & 255u : (a + av) & 255u;
+        a = (uint32_t)__builtin_amdgcn_readlane((int)ares, 63);
+        pend = (uint32_t)__builtin_amdgcn_readlane((int)adw, 63 - __builtin_clzll(lives));               // (lane 0 is live)
+        // top, where it was produced before this group: the pixel's index in the image is done + pix
+        const uint32_t topkind = done + pix < w ? 0u : pix < w ? 1u : 2u;      // the left pixel (row 0) / fetched here / made in this group
+        uint32_t topv = 0;
+        if (pixop && type == kPDiff && topkind == 1u) { const uint32_t xi = x + pix; topv = rowb[(xi >= w ? xi - w : xi) * outc]; }
+        // the chain, one straight-line step for every kind of op: l = ((top + left + 1) >> 1) + d, where an absolute op has top = left
+        // = 0 and d = its value, and a REPEAT has top = left and d = 0 ((2 l + 1) >> 1 = l).  bit 8: left is the previous luminance
+        // (else 0); bit 9: top is that same value (row 0, REPEAT); bit 10: top was made in this group
+        const bool diff = type == kPDiff;
+        const uint32_t opw = (val & 255u) | (type != kPAbs ? 0x100u : 0u) | (type == kPRep || (diff && topkind == 0u) ? 0x200u : 0u) |
+                             (diff && topkind == 2u ? 0x400u : 0u);
+        const uint64_t pixops = __ballot(pixop);
+        uint32_t lres = 0;
+        for (uint64_t m = pixops; m; m &= m - 1ull) {
+            const int j = __builtin_ctzll(m);
+            const uint32_t ow = (uint32_t)__builtin_amdgcn_readlane((int)opw, j);
+            uint32_t top = (uint32_t)__builtin_amdgcn_readlane((int)topv, j);
+            const uint32_t left = (ow & 0x100u) ? l : 0u;
+            if (ow & 0x400u) {                                                 // the pixel op of this group that covers pixel pix - w
+                const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)pix, j) - w;
+                top = (uint32_t)__builtin_amdgcn_readlane((int)lres, 63 - __builtin_clzll(__ballot(pixop && pix <= t)));
+            }
+            top = (ow & 0x200u) ? left : top;
+            l = (((top + left + 1u) >> 1) + ow) & 255u;
+            lres = lane == (uint32_t)j ? l : lres;
+        }
+        // the pixels, row piece by row piece
+        const uint32_t pv = lres | ares << 8;
+        uint64_t runs = __ballot(pixop && cnt > 1u);
+        for (uint32_t gp = 0; gp < group; ) {
+            const uint32_t m = min(group - gp, w - x);
+            wave_order();
+            if (pixop && cnt == 1u && pix - gp < m) store(x + pix - gp, pv);
+            for (uint64_t rm = runs; rm; rm &= rm - 1ull) {
+                const int j = __builtin_ctzll(rm);
+                const uint32_t s = (uint32_t)__builtin_amdgcn_readlane((int)pix, j), e = s + (uint32_t)__builtin_amdgcn_readlane((int)cnt, j),
+                               v = (uint32_t)__builtin_amdgcn_readlane((int)pv, j);
+                if (s >= gp + m) break;
+                if (e <= gp + m) runs &= ~(1ull << j);                         // ends in this piece
+                for (uint32_t k = max(s, gp) + lane; k < min(e, gp + m); k += kWave) store(x + k - gp, v);
+            }
+            x += m; gp += m;
+            if (x == w) {
+                wave_order();
+                flush_run<kWave>(row, dst + (uint64_t)y * w * outc, w * outc, lane);
+                x = 0; ++y;
+            }
+        }
+        done += group;
+        np += 64u + leaves;
+    }
+    return true;
+}
+
+__global__ void __launch_bounds__(kWave) k_qoix_plane(const QxImg* __restrict__ imgs, uint8_t* out, uint32_t* status)
+{
+    __shared__ uint32_t row[kPlaneCap / 2 + 8];
+    const QxImg im = imgs[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    if (status[im.status]) return;                                             // the LZ4 block was refused
+    const bool ok = im.w > kPlaneCap ? plane_decode<true>(im, im.wide_row, out, lane) : plane_decode<false>(im, row, out, lane);
+    if (!ok && lane == 0) atomicOr(&status[im.status], 2u);
+}
+
+// Measurements (tools/qoix_bench.py, tools/qoix_plane_bench.py): with GAMUT_HIP_QOIX_TIMING=1 the decode call brackets each of its
+// kernels -- not the upload -- with events and keeps the GPU times of the calling thread's last call; the blob is resident in HBM when
+// the first event is reached.
+thread_local float t_last_ms[3] = { -1.0f, -1.0f, -1.0f };
 
 int decode_batch(const uint8_t* const* data, const size_t* len, int count, int channels, const int64_t* out_offset, uint8_t* out,
                  gamut_hip_qoix_info* info, int* status_host, hipStream_t stream)
@@ -288,8 +465,12 @@ int decode_batch(const uint8_t* const* data, const size_t* len, int count, int c
         if (info) info[i] = qi;
         if (status_host) status_host[i] = GAMUT_HIP_OK;
         if (rc == GAMUT_HIP_OK && out_offset[i] < 0) rc = set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoix: negative out_offset");
+        const bool plane = qi.channels < 3;                                    // (only with the switch on does such a header pass)
+        if (rc == GAMUT_HIP_OK && channels && (channels < 3) != plane)
+            rc = set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoix: %d channels asked of a %d-channel file (1 / 2 are for grey files, 3 / 4 for colour files)", channels, qi.channels);
         if (rc != GAMUT_HIP_OK) { refuse(i, rc); continue; }
         QxImg im{};
+        im.plane = plane;
         im.out_off = out_offset[i]; im.avail = size; im.w = (uint32_t)qi.width; im.h = (uint32_t)qi.height;
         im.outc = (uint32_t)(channels ? channels : qi.channels);
         im.status = (uint32_t)imgs.size();
@@ -297,7 +478,8 @@ int decode_batch(const uint8_t* const* data, const size_t* len, int count, int c
         cursor = up16(cursor + len[i] + 8) + 16;
         size_t s = (size_t)-1, wr = (size_t)-1;
         if (qi.compression == 1) { s = scratch; scratch += up16((size_t)size + 8) + 16; }      // header-sized gap + orig bytes, read by whole dwords
-        if (im.w > kRowCap) { wr = scratch; scratch += up16(((size_t)im.w + 8) * 4); }
+        if (plane) { if (im.w > kPlaneCap) { wr = scratch; scratch += up16((size_t)im.w * 2 + 48); } }
+        else if (im.w > kRowCap) { wr = scratch; scratch += up16(((size_t)im.w + 8) * 4); }
         slot.push_back(s); wide.push_back(wr);
         imgs.push_back(im); which.push_back(i);
     }
@@ -327,16 +509,23 @@ int decode_batch(const uint8_t* const* data, const size_t* len, int count, int c
             if (wide[k] != (size_t)-1) imgs[k].wide_row = (uint32_t*)(d + staged + wide[k]);
         }
         memset(h + cursor, 0, staged - cursor);
-        memcpy(h + o_img, imgs.data(), n * sizeof(QxImg));
+        size_t ncol = 0;                                                       // the colour records first, then the plane records
+        for (size_t k = 0; k < n; ++k) ncol += !imgs[k].plane;
+        for (size_t k = 0, c = 0, p = ncol; k < n; ++k) memcpy(h + o_img + (imgs[k].plane ? p++ : c++) * sizeof(QxImg), &imgs[k], sizeof(QxImg));
         if (nlz) memcpy(h + o_lz, lzs.data(), nlz * sizeof(QxLz));
         GAMUT_HIP_CHECK(hipMemcpyAsync(d, h, staged, hipMemcpyHostToDevice, stream));
         static const bool timing = env_flag("GAMUT_HIP_QOIX_TIMING");
-        KernelTimer<3> timer(timing);
+        KernelTimer<4> timer(timing);
         timer.mark(stream);
         if (nlz) hipLaunchKernelGGL(k_qoix_lz4, dim3((uint32_t)nlz), dim3(kWave), 0, stream, (const QxLz*)(d + o_lz), (uint32_t*)(d + o_st));
         timer.mark(stream);
-        hipLaunchKernelGGL(k_qoix_avg, dim3((uint32_t)n), dim3(kWave), 0, stream, (const QxImg*)(d + o_img), out, (uint32_t*)(d + o_st));
+        if (ncol) hipLaunchKernelGGL(k_qoix_avg, dim3((uint32_t)ncol), dim3(kWave), 0, stream, (const QxImg*)(d + o_img), out, (uint32_t*)(d + o_st));
         if (int rc = launch_status("qoix_decode")) return rc;
+        timer.mark(stream);
+        if (n > ncol) {                                                        // a third launch only when the batch holds a plane file
+            hipLaunchKernelGGL(k_qoix_plane, dim3((uint32_t)(n - ncol)), dim3(kWave), 0, stream, (const QxImg*)(d + o_img) + ncol, out, (uint32_t*)(d + o_st));
+            if (int rc = launch_status("qoix_decode (plane)")) return rc;
+        }
         timer.mark(stream);
         GAMUT_HIP_CHECK(hipMemcpyAsync(h + o_st, d + o_st, n * 4, hipMemcpyDeviceToHost, stream));
         GAMUT_HIP_CHECK(hipStreamSynchronize(stream));
@@ -360,8 +549,9 @@ int gamut_hip_qoix_decode_batch_device(const uint8_t* const* data, const size_t*
                                        uint8_t* out, gamut_hip_qoix_info* info, int* status_host, void* stream)
 {
     clear_error();
-    if (count < 0 || (channels != 0 && channels != 3 && channels != 4) || (count > 0 && (!data || !len || !out_offset || !out)))
-        return set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoix_decode_batch_device: bad arguments (channels is 0, 3 or 4)");
+    const bool grey = (channels == 1 || channels == 2) && qoix_plane_on();
+    if (count < 0 || (channels != 0 && channels != 3 && channels != 4 && !grey) || (count > 0 && (!data || !len || !out_offset || !out)))
+        return set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoix_decode_batch_device: bad arguments (channels is 0, 3 or 4; 1 or 2 with gamut_hip_qoix_set_plane(1))");
     if (count == 0) return GAMUT_HIP_OK;
     if (!have_device()) return GAMUT_HIP_ERR_NO_DEVICE;
     try {
@@ -403,8 +593,10 @@ void* gamut_hip_qoix_lz4_decode(const void* data, int size, gamut_hip_qoix_info*
 }
 
 int gamut_hip_qoix_row_capacity(void) { return (int)kRowCap; }
+int gamut_hip_qoix_plane_row_capacity(void) { return (int)kPlaneCap; }
 
 float gamut_hip_qoix_last_decode_kernel_ms(void) { return t_last_ms[0] < 0 || t_last_ms[1] < 0 ? -1.0f : t_last_ms[0] + t_last_ms[1]; }
 float gamut_hip_qoix_last_decode_stage_ms(int stage) { return stage == 0 || stage == 1 ? t_last_ms[stage] : -1.0f; }
+float gamut_hip_qoix_last_plane_kernel_ms(void) { return t_last_ms[2]; }
 
 } // extern "C"

@@ -12,6 +12,11 @@
 // else the container accepts is GAMUT_HIP_ERR_UNSUPPORTED.  Then QOI2AVG's header checks (qoi2avg.d:634-666) on the size the sub-codec
 // sees: size >= 29, width and height non-zero, colorspace <= 2, version <= 1, the signature, height < 400000000 / width (unsigned).
 //
+// 8-bit files with 1 or 2 channels are QOI-Plane (source/gamut/codecs/qoiplane.d), built behind the process-wide switch
+// gamut_hip_qoix_set_plane (initial value GAMUT_HIP_QOIX_PLANE=0|1, default 0).  Off, they are GAMUT_HIP_ERR_UNSUPPORTED as before the
+// codec existed; on, they go through qoiplane_decode's own checks (qoiplane.d:379-411), which are QOI2AVG's with colorspace <= 1: a
+// colorspace-2 file with 2 channels is typed lap8 by the container and then refused by the sub-codec.
+//
 // An early refusal that the reference does not have, and that never changes a verdict: an LZ4 block of n bytes cannot produce more
 // than 255 * n bytes.  Proof, per input byte: a literal yields itself (1 byte); a length-extension byte adds at most 255 to a
 // literal or match length (255 bytes, and the literal ones need their own input bytes on top); a token yields at most its 15 + 4
@@ -19,9 +24,17 @@
 // "input exhausted" (deviation 1 of qoix.hip), and is refused here before any scratch is sized from the claim.
 // tests/test_qoix_cpu.py asserts that this test never disagrees with the restatement.
 #include "common.hpp"
+#include <atomic>
 #include <climits>
 
 namespace gamut {
+
+static std::atomic<int>& plane_switch()
+{
+    static std::atomic<int> on{ [] { const char* e = getenv("GAMUT_HIP_QOIX_PLANE"); return e && e[0] == '1' && !e[1] ? 1 : 0; }() };
+    return on;
+}
+bool qoix_plane_on() { return plane_switch().load(std::memory_order_relaxed) != 0; }
 
 int qoix_fail(const char* why) { return set_error(GAMUT_HIP_ERR_DECODE, "qoix: %s", why); }
 
@@ -57,13 +70,14 @@ int qoix_parse_header(const uint8_t* data, size_t len, gamut_hip_qoix_info* info
         if (info->orig < 0) return qoix_fail("negative original size");
         size = 25u + (uint32_t)info->orig;
     } else if (info->compression != 0) return qoix_fail("compression other than 0 / 1");      // :417-418
-    if (depth == 10 || ch < 3)
+    const bool plane = depth == 8 && ch < 3;
+    if (depth == 10 || (plane && !qoix_plane_on()))
         return set_error(GAMUT_HIP_ERR_UNSUPPORTED, "qoix: the %d-bit %d-channel codec is not built yet", depth, ch);
-    // qoix_decode qoi2avg.d:634-666
+    // qoix_decode qoi2avg.d:634-666, qoiplane_decode qoiplane.d:379-411
     if (size < 29) return qoix_fail("no room for the 4 closing bytes");
     const uint32_t w = (uint32_t)info->width, h = (uint32_t)info->height;
     if (w == 0 || h == 0) return qoix_fail("zero width or height");
-    if (info->colorspace > 2) return qoix_fail("colorspace above 2");
+    if (info->colorspace > (plane ? 1 : 2)) return qoix_fail(plane ? "colorspace above 1 in a QOI-Plane file" : "colorspace above 2");
     if (info->version > 1) return qoix_fail("version above 1");
     if (!info->detected) return qoix_fail("bad signature");
     if (h >= 400000000u / w) return qoix_fail("too many pixels");
@@ -81,4 +95,10 @@ extern "C" int gamut_hip_qoix_read_header(const uint8_t* data, size_t len, gamut
     clear_error();
     if (!info) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoix_read_header: info is NULL");
     return qoix_parse_header(data, len, info, nullptr);
+}
+
+extern "C" int gamut_hip_qoix_set_plane(int on)
+{
+    if (on != 0 && on != 1) return plane_switch().load(std::memory_order_relaxed);
+    return plane_switch().exchange(on, std::memory_order_relaxed);
 }

@@ -821,14 +821,21 @@ float   gamut_hip_dds_last_encode_kernel_ms(void);
  * the file's own channel count; the last four bytes are never decoded as opcodes and never checked; a stream that ends early repeats
  * the last pixel and surplus ops are ignored; runs cross row ends and are cut at the image's end; a 3-channel file may carry ADIFF
  * and RGBA ops, whose alpha shows when 4 channels are asked for; whatever follows the LZ4 block's final literal run is ignored.
- * The grey codecs (8-bit with 1 or 2 channels) and the 10-bit codecs are not built yet: GAMUT_HIP_ERR_UNSUPPORTED.
+ * The 10-bit codecs are not built yet: GAMUT_HIP_ERR_UNSUPPORTED.  The grey codec (8-bit with 1 or 2 channels: QOI-Plane,
+ * qoiplane_decode, codecs/qoiplane.d:377-541) is built behind the process-wide switch gamut_hip_qoix_set_plane, whose default keeps
+ * such files GAMUT_HIP_ERR_UNSUPPORTED.  With the switch on they decode to l8 / la8 (lap8 never: QOI-Plane refuses colorspace 2), bit
+ * for bit.  Kept from the reference there: the closing four bytes ARE decoded (f ff is "repeat to the end", which is how a stream
+ * ends); a stream that ends that way early repeats the last pixel; surplus ops are ignored; runs cross row ends; a DIRECT in a
+ * 2-channel file sets luminance only; 1 channel asked of a 2-channel file drops alpha, 2 asked of a 1-channel file gives 255 unless
+ * ADIFF / LA ops set it.
  * Deliberate deviations, each where the reference touches memory it does not own, each GAMUT_HIP_ERR_DECODE:
  *   1. LZ4: any read at or past the end of the file refuses the file (the reference has no input bound);
  *   2. LZ4: offset 0, or a match that starts before the first output byte, refuses the file (the reference reads up to 64 KiB in
  *      front of its buffer);
  *   3. QOI2AVG: an END opcode that is executed refuses the file (the reference leaves the rest of the row as whatever its scanline
  *      buffer held, uninitialised memory in rows 0 and 1); no valid file executes END;
- *   4. QOI2AVG: an op byte read at index >= size refuses the file (an ADIFF chain running through the last four bytes).
+ *   4. QOI2AVG: an op byte read at index >= size refuses the file (an ADIFF chain running through the last four bytes);
+ *  P1. QOI-Plane: a nibble read at byte index >= size refuses the file (the reference has no input bound).
  * Also refused: a length above INT_MAX (loadQOIX keeps it in an int), and an `orig` above 255 * (length - 29), which no LZ4 block
  * of that length can produce (it could only end in deviation 1).
  * (Declared typedef-first: the layout of this struct is pinned by tests/c/qoix_abi_layout.c and tests/test_qoix_cpu.py.) */
@@ -844,12 +851,13 @@ struct gamut_hip_qoix_info {
 };
 /* the header alone (host, no GPU needed).  info->detected is detectQOIX's verdict, the return value the load's on everything that
  * is decidable without the body: GAMUT_HIP_OK, GAMUT_HIP_ERR_UNSUPPORTED for a header the container accepts but whose codec is not
- * built yet (bitdepth 10, or 8-bit with 1 or 2 channels), GAMUT_HIP_ERR_DECODE for a refusal.  Fields are filled as far as the
- * header was read. */
+ * built yet (bitdepth 10, or 8-bit with 1 or 2 channels while gamut_hip_qoix_set_plane is off), GAMUT_HIP_ERR_DECODE for a refusal.
+ * Fields are filled as far as the header was read.  With the switch on an 8-bit 1- or 2-channel header goes through
+ * qoiplane_decode's checks (QOI2AVG's, with colorspace <= 1: a 2-channel file of colorspace 2 has pixel_type lap8 and is refused). */
 int gamut_hip_qoix_read_header(const uint8_t* data, size_t len, gamut_hip_qoix_info* info);
 /* `count` QOIX files in host memory -> tight rows of width * channels bytes at out + out_offset[i] (device, any alignment).
  * channels 0: the file's own count; 3 / 4 as in qoix_decode (alpha dropped / kept, 255 unless ADIFF or RGBA ops set it); anything
- * else is GAMUT_HIP_ERR_INVALID_ARG.  Two launches whatever the batch holds: one over the LZ4 files (a wave each; skipped when there
+ * else is GAMUT_HIP_ERR_INVALID_ARG (for 1 / 2 see gamut_hip_qoix_set_plane).  Two launches whatever a batch of colour files holds: one over the LZ4 files (a wave each; skipped when there
  * are none), one over all op streams (a wave each).  info[i] / status_host[i] (either may be NULL) per file; a failing file gets its
  * status and does not disturb the others; returns the status of the lowest-numbered failing file, whose number the tail of
  * last_error names ("image %d:").  A file refused on the host writes nothing; one refused on the device (the verdict is the
@@ -867,6 +875,18 @@ int   gamut_hip_qoix_row_capacity(void);
  * decoded or `stage` is out of range */
 float gamut_hip_qoix_last_decode_kernel_ms(void);
 float gamut_hip_qoix_last_decode_stage_ms(int stage);
+/* The QOI-Plane switch, process-wide: `on` is 0 or 1, the previous value is returned, any other argument changes nothing (and
+ * returns the current value).  Initial value: GAMUT_HIP_QOIX_PLANE=0|1 in the environment, default 0.  Off, every QOIX entry behaves
+ * as it did before the codec existed.  On, 8-bit files with 1 or 2 channels decode through every QOIX entry and Image.loadFromMemory;
+ * gamut_hip_qoix_decode_batch_device then also takes channels 1 / 2, which apply to grey files as 3 / 4 apply to colour files: a file
+ * of the other family gets GAMUT_HIP_ERR_INVALID_ARG as its status, writes nothing and does not disturb its neighbours (channels 0
+ * suits a mixed batch).  Grey files run in a third launch, k_qoix_plane (a wave each), skipped when the batch holds none. */
+int   gamut_hip_qoix_set_plane(int on);
+/* k_qoix_plane keeps rows of up to this many pixels in LDS; a wider row lives in a global scratch row */
+int   gamut_hip_qoix_plane_row_capacity(void);
+/* GPU milliseconds of k_qoix_plane in the calling thread's last decode call, under GAMUT_HIP_QOIX_TIMING=1 as the getters above (whose
+ * values do not include it); -1 when timing is off or nothing was decoded */
+float gamut_hip_qoix_last_plane_kernel_ms(void);
 /* Encode: byte for byte qoix_lz4_encode (plugins/qoix.d:251-339) as saveQOIX drives it (:156-242) for 8-bit rgb / rgba -- the 25
  * header bytes, the op stream of qoix_encode (codecs/qoi2avg.d:376-615) with its four 0xff bytes, the LZ4 block of LZ4_compress on a
  * 64-bit build (codecs/lz4.d:289-554: byU16 below 65547 input bytes, byU32 from there) and the choice between the two files.  Kept
