@@ -278,7 +278,8 @@ extern(C)
     float gamut_hip_qoix_last_decode_stage_ms(int stage);
     // QOI-Plane (8-bit files with 1 or 2 channels, codecs/qoiplane.d:377-541) behind a process-wide switch: set_plane(0 | 1) returns the
     // previous value (any other argument changes nothing); the initial value is GAMUT_HIP_QOIX_PLANE=0|1, default 0 (such files are
-    // GAMUT_HIP_ERR_UNSUPPORTED).  On: l8 / la8 decode, channels 1 / 2 accepted for grey files.
+    // GAMUT_HIP_ERR_UNSUPPORTED).  On: l8 / la8 decode, channels 1 / 2 accepted for grey files, and the encode entries take
+    // descriptions with 1 / 2 channels (QOI-Plane, qoiplane_encode).
     int   gamut_hip_qoix_set_plane(int on);
     int   gamut_hip_qoix_plane_row_capacity();
     float gamut_hip_qoix_last_plane_kernel_ms();
@@ -291,11 +292,13 @@ extern(C)
                                              const(long)* out_offset, ubyte* out_, long* out_len, int* status_host, void* stream);
     void* gamut_hip_qoix_write_to_mem(const(void)* data, int pitch, const(gamut_hip_qoix_desc)* desc, int* out_len);
     int   gamut_hip_qoix_encode_window();
+    int   gamut_hip_qoix_plane_encode_segment();
     int   gamut_hip_lz4_compress_bound(int n);
     int   gamut_hip_lz4_compress_batch_device(const(ubyte*)* src, const(int)* len, int count, const(long)* out_offset, ubyte* out_,
                                               long* out_len, int* status_host, void* stream);
     float gamut_hip_qoix_last_encode_kernel_ms();
     float gamut_hip_qoix_last_encode_stage_ms(int stage);
+    float gamut_hip_qoix_last_plane_encode_stage_ms(int stage);
 
     // ---- any of the three formats, one call (image.d:1045-1061 identifyFormatFromStream + g_plugins[fif].loadProc, batched) ----
     struct gamut_hip_image_info { int format, width, height, channels_in_file, channels; }

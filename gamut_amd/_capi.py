@@ -185,10 +185,12 @@ SIGNATURES = {
                                             C.POINTER(_i64), _pi, _vp]),
     "gamut_hip_qoix_write_to_mem": (_vp, [_vp, _i, C.POINTER(QoixDesc), _pi]),
     "gamut_hip_qoix_encode_window": (_i, []),
+    "gamut_hip_qoix_plane_encode_segment": (_i, []),
     "gamut_hip_lz4_compress_bound": (_i, [_i]),
     "gamut_hip_lz4_compress_batch_device": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, C.POINTER(_i64), _vp, C.POINTER(_i64), _pi, _vp]),
     "gamut_hip_qoix_last_encode_kernel_ms": (_f, []),
     "gamut_hip_qoix_last_encode_stage_ms": (_f, [_i]),
+    "gamut_hip_qoix_last_plane_encode_stage_ms": (_f, [_i]),
     "gamut_hip_sqz_read_header": (_i, [_vp, _sz, C.POINTER(SqzInfo)]),
     "gamut_hip_sqz_decode_coeffs": (_i, [_vp, _sz, _vp, _sz, C.POINTER(SqzInfo)]),
     "gamut_hip_sqz_reconstruct_batch_device": (_i, [_vp, C.POINTER(SqzDesc), _i, C.POINTER(_i64), _vp, _pi, _vp]),

@@ -668,14 +668,15 @@ uint8_t* save_tga(gamut_image* img, int, size_t* len)
         [&](OneImage& b) { return gamut_hip_tga_encode_batch_device(&b.src, &b.pitch, &w, &h, &comp, nullptr, 1, &b.out_offset, b.out, &b.len, &b.status, b.stream); });
 }
 
-// saveQOIX (plugins/qoix.d:156-242), the 8-bit colour slice: rgb8 / rgba8 / rgbap8 (colorspace 2), layer 0, the image's pixel aspect
-// ratio and vertical DPI in the header, LZ4 when it is smaller; grey and 16-bit types wait for their codecs; flags ignored
+// saveQOIX (plugins/qoix.d:156-242), the 8-bit types: rgb8 / rgba8 / rgbap8 (colorspace 2) and, while the QOI-Plane switch is on
+// (gamut_hip_qoix_set_plane; off, the bound refuses them), l8 / la8 / lap8 (colorspace 2); layer 0, the image's pixel aspect ratio and
+// vertical DPI in the header, LZ4 when it is smaller; 16-bit types wait for their codec; flags ignored
 uint8_t* save_qoix(gamut_image* img, int, size_t* len)
 {
     gamut_hip_qoix_desc d{};
     d.width = img->_width; d.height = img->_height;
-    d.channels = img->_type == GAMUT_PIXEL_rgbap8 ? 4 : channels8(img->_type) >= 3 ? channels8(img->_type) : 0;
-    d.colorspace = img->_type == GAMUT_PIXEL_rgbap8 ? 2 : 0;
+    d.channels = img->_type == GAMUT_PIXEL_rgbap8 ? 4 : img->_type == GAMUT_PIXEL_lap8 ? 2 : channels8(img->_type);
+    d.colorspace = img->_type == GAMUT_PIXEL_rgbap8 || img->_type == GAMUT_PIXEL_lap8 ? 2 : 0;
     d.mode = 0;
     d.pixel_aspect_ratio = img->_pixelAspectRatio; d.resolution_y = img->_resolutionY;
     if (!d.channels || img->_layerCount < 1 || gamut_hip_qoix_encode_bound(&d) < 0) return nullptr;

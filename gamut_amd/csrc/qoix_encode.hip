@@ -1,4 +1,4 @@
-// qoix_encode.hip -- QOIX colour files on the GPU: the bytes of qoix_lz4_encode (source/gamut/plugins/qoix.d:251-339) as saveQOIX
+// qoix_encode.hip -- QOIX 8-bit files on the GPU, colour and (behind the QOI-Plane switch) grey: the bytes of qoix_lz4_encode (source/gamut/plugins/qoix.d:251-339) as saveQOIX
 // drives it (:156-242) for 8-bit rgb / rgba, that is the QOI2AVG op stream of qoix_encode (source/gamut/codecs/qoi2avg.d:376-615), the
 // LZ4 block of LZ4_compress on a 64-bit build (source/gamut/codecs/lz4.d:289-554) and the rule that the smaller file wins, many images
 // per call.
@@ -32,14 +32,45 @@
 //                 16: a byte head and tail, 16-byte pieces between).
 // Nothing outside [out_offset, out_offset + out_len) is written.
 //
+// Grey: 1 or 2 channels are QOI-Plane (qoiplane_encode, source/gamut/codecs/qoiplane.d:109-365), accepted while the process-wide switch
+// of qoix_host.hip is on (gamut_hip_qoix_set_plane / GAMUT_HIP_QOIX_PLANE: "the QOI-Plane codec is on", in both directions); off, such a
+// description is refused as before the codec existed.  The ops sit on nibble boundaries, high nibble first; the state starts as
+// {l: 0, a: 255}; a run is cut at 258 pixels, at the image's last pixel and in front of a pixel that differs.  This encoder has no
+// serial chain at all: the predecessor, the pixel above and the run count are input, so an image is cut into segments of kSeg
+// consecutive pixels of the raster (whatever the width is) and a wave takes a segment 64 pixels at a time.  Only the distance to the
+// last pixel that differed, modulo 258, crosses a segment boundary.  Three more launches, whatever the batch's grey images are:
+//   k_qpenc_count  a wave per segment: the repeats in front of its first differing pixel, that pixel's place (or none), the nibbles of
+//                  everything behind the leading stretch and the last of them.  What the leading stretch emits is a closed form of
+//                  its length and the entering run count e (qp_lead), so it is left to the scan;
+//   k_qpenc_scan   a wave per image over its segments, 64 at a time: e (a prefix maximum of the last differing pixel), the first
+//                  nibble (a prefix sum), the nibble in front of it (a prefix "last that exists") and the image's stored length;
+//   k_qpenc_write  a wave per segment: the ops again, OR-ed as nibbles into the zeroed LDS stage (ds atomics on the stage only) and out
+//                  through flush_run.  Byte ownership is fixed: a segment that starts on an odd nibble writes the shared byte whole
+//                  (the carried nibble high, its own first low), one that ends on an odd nibble leaves its half byte to the next
+//                  segment that emits; the segment with the last pixel writes the closing nibbles, the first one the header.
+// k_qxenc_lz4 and k_qxenc_pick then serve grey and colour images alike.  A batch without grey images issues the three launches above,
+// one without colour images does not launch k_qxenc_ops.
+//
+// The bound.  The stored stream behind the header has at most datalen_max = (w * h * n + 10) / 2 bytes, n = 3 nibbles a pixel for 1
+// channel and 6 for 2: the ops, the nine closing nibbles and one more to end on a byte.  The bound is 29 + datalen_max +
+// datalen_max / 255 + 16, as for colour.
+//
 // DELIBERATE DEVIATIONS.
 //   1. For 4 channels the reference copies pitchBytes into a scanline buffer of 4 * width bytes: a padded pitch overruns it, a negative
 //      one is a huge memcpy.  Here width * channels bytes of every row are read, whatever the pitch is.
 //   2. The reference's int max_size wraps for large shapes; a description whose bound exceeds 2^31 - 1 is refused instead.
+//   G1. qoiplane_encode allocates (w * h * n + 1) / 2 + 29 bytes, one too few whenever every pixel takes its worst op and w * h * n is
+//       even (1 x n images alternating 100 / 200, n = 1..39: all 39 two-channel shapes and the 19 even one-channel ones overrun it;
+//       tests/test_qoix_plane_encode_cpu.py).  The file's content is well defined all the same; the bound here is the true maximum.
+//   G2. w * h * 6 above 2^31 - 1 (2 channels, more than 357913941 pixels) is refused: the reference's int size wraps there.
+//   Padded and negative pitches are honoured as the reference honours them for grey: width * channels bytes of a row are read.
 #include "encode_host.hpp"
 #include "device_util.hpp"
 
 namespace gamut {
+
+bool qoix_plane_on();                                                        // qoix_host.hip: gamut_hip_qoix_set_plane / GAMUT_HIP_QOIX_PLANE
+
 namespace {
 
 constexpr int kWave = 64;
@@ -50,6 +81,10 @@ constexpr uint32_t kPixelsMax = 400000000u;
 constexpr int kPickBlocks = 32, kPickThreads = 256;
 constexpr int kAhead = 4;                                                    // groups of 64 pixels fetched ahead
 constexpr uint32_t kLz64K = 65547u, kLzMaxInput = 0x7E000000u;
+constexpr uint32_t kSeg = 4096;                                              // QOI-Plane: pixels of a segment, a multiple of 64 whatever the width is
+constexpr uint32_t kRunMax = 258, kNoNibble = 0xffu;
+constexpr uint32_t kQpFlushAt = 2048;                                        // bytes assembled in LDS between two flushes
+constexpr uint32_t kQpStageDwords = (kQpFlushAt + 9 * kWave / 2) / 4 + 8;    // + one group's worst case (9 nibbles a pixel), spare dwords for flush_run
 
 struct QeImg {
     const uint8_t* src; int64_t pitch;
@@ -62,6 +97,12 @@ struct LzJob {
     const uint8_t* src; uint8_t* dst;                                        // header 1: a stored file and a candidate file; 0: bytes and block
     uint32_t len, header, slot, pad;                                         // header 1: the length is file_len[slot] - 25
 };
+struct QpImg { QeImg im; uint32_t seg0, nseg; };                            // a grey image and the number of its first segment in the batch
+struct QpSeg {                                                               // k_qpenc_count, per segment
+    int32_t last_diff;                                                       // the last pixel (raster index) that differs from its predecessor, -1: none
+    uint32_t lead, rest, rest_last;                                          // repeats in front of the first such pixel; nibbles behind them, the last of those
+};
+struct QpPlace { uint32_t e, off, carry, pad; };                             // k_qpenc_scan: entering run count, first nibble, the nibble in front of it
 struct PickJob { const uint8_t* stored; const uint8_t* cand; uint8_t* dst; uint32_t slot, pad; };
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
@@ -243,6 +284,226 @@ __global__ void __launch_bounds__(kWave) k_qxenc_ops(const QeImg* __restrict__ i
     if (lane == 0) file_len[im.slot] = written + fill;
 }
 
+// ---- QOI-Plane (qoiplane.d:109-365) -------------------------------------------------------------------------------------------------
+
+// The op nibbles of a pixel v = l | a << 8 that differs from its predecessor `prev` (:257-306), first nibble in bits 0..3, the count in
+// *len (at most 6).  `top` is channel 0 of the pixel above, prev's in row 0.
+__device__ __forceinline__ uint32_t qp_op(uint32_t v, uint32_t prev, uint32_t top, uint32_t* len)
+{
+    const uint32_t l = v & 255u, a = v >> 8, rl = prev & 255u;
+    const int va = (int8_t)(a - (prev >> 8));
+    uint32_t out = 0, n = 0;
+    if (va) {
+        if (va < -7 || va > 7) { *len = 6; return 0xbu | (l >> 4) << 8 | (l & 15u) << 12 | (a >> 4) << 16 | (a & 15u) << 20; }       // LA
+        out = 0xbu | (uint32_t)(va + 8) << 4; n = 2;                          // ADIFF
+    }
+    const int d = (int8_t)(l - ((top + rl + 1u) >> 1));
+    uint32_t op, m;
+    if (d >= -4 && d <= 3) { op = (uint32_t)(d + 4); m = 1; }
+    else if (d >= -16 && d <= 15) { const uint32_t b = 0x80u | (uint32_t)(d + 16); op = b >> 4 | (b & 15u) << 4; m = 2; }
+    else { op = 0xau | (l >> 4) << 4 | (l & 15u) << 8; m = 3; }
+    *len = n + m;
+    return out | op << (4 * n);
+}
+
+// encodeRun :191-216 for 1..258 pixels, as nibbles
+__device__ __forceinline__ uint32_t qp_run(uint32_t run, uint32_t* len)
+{
+    if (run <= 3) { *len = 1; return 0xcu | (run - 1); }
+    *len = 3;
+    return 0xfu | ((run - 4) >> 4) << 4 | ((run - 4) & 15u) << 8;
+}
+
+// What the repeats in front of a segment's first differing pixel emit, as a function of their number `lead` and of the run count
+// `e` (0..257) that enters the segment: a REPEAT2 of 258 whenever the count gets there, and the rest when the stretch ends at a pixel
+// that differs or at the image's last pixel (`closed`).  Returns the nibble count; *last is the last nibble, kNoNibble when none.
+__device__ __forceinline__ uint32_t qp_lead(uint32_t e, uint32_t lead, bool closed, uint32_t* last)
+{
+    const uint32_t t = e + lead, full = t / kRunMax, r = t - full * kRunMax;
+    uint32_t n = 3 * full;
+    *last = full ? 0xeu : kNoNibble;                                         // f f e: 258 - 4
+    if (closed && r) { uint32_t m; const uint32_t nib = qp_run(r, &m); n += m; *last = (nib >> (4 * (m - 1))) & 15u; }
+    return n;
+}
+
+// A segment of the raster, 64 pixels at a time: every lane computes its pixel's predecessor, the pixel above and its nibbles from the
+// source.  kWrite false (k_qpenc_count): what lies behind the leading repeats is counted, the first differing pixel without the run
+// in front of it (that run belongs to the leading stretch, whose emission depends on e).  kWrite true (k_qpenc_write): e is known,
+// so the leading stretch is like any other; the nibbles are OR-ed into the zeroed LDS stage and leave through flush_run.
+template <bool kWrite> __device__ __forceinline__ void qp_segment(const QpImg& qi, uint32_t seg, QpSeg* rec, const QpPlace* place, uint32_t* stage)
+{
+    const QeImg& im = qi.im;
+    const uint32_t lane = threadIdx.x, w = im.w, ch = im.ch, total = im.w * im.h;
+    const uint64_t lt = (1ull << lane) - 1;
+    const uint32_t s0 = seg * kSeg, s1 = min(total, s0 + kSeg);
+    const bool holds_last = s1 == total;
+    const uint64_t magic = w > 1 ? ~0ull / w + 1 : 0;                        // i / w = the high half of i * magic for every i < 2^32
+    auto row_of = [&](uint32_t i) -> uint32_t { return w > 1 ? (uint32_t)__umul64hi((uint64_t)i, magic) : i; };
+    auto pixel = [&](uint32_t i, uint32_t* top) -> uint32_t {               // i < total: every address is inside the image
+        const uint32_t y = row_of(i), x = i - y * w;
+        const uint8_t* p = im.src + (int64_t)y * im.pitch + (size_t)x * ch;
+        *top = y > 0 ? (uint32_t)*(p - im.pitch) : 256u;                     // 256: row 0, the predecessor stands in
+        return p[0] | (ch == 2 ? (uint32_t)p[1] : 255u) << 8;
+    };
+    uint32_t dummy;
+    uint32_t last_v = s0 ? rfl(pixel(s0 - 1, &dummy)) : 0xFF00u;             // the state starts as {l: 0, a: 255}
+    int32_t ld;                                                              // the last pixel that differed, or what stands for it
+    bool seen = kWrite;
+    uint32_t fill = 0, written = 0, lead = 0, rest = 0, rest_last = kNoNibble;
+    uint8_t* dst = im.dst;
+    if (kWrite) {
+        const QpPlace pl = place[qi.seg0 + seg];
+        ld = (int32_t)s0 - 1 - (int32_t)pl.e;
+        for (uint32_t k = lane; k < kQpStageDwords; k += kWave) stage[k] = 0;
+        wave_order();
+        if (seg == 0) {
+            if (lane < kHeader) {                                            // :151-160
+                const uint32_t word = lane < 4 ? 0x716F6978u : lane < 8 ? w : lane < 12 ? im.h : lane < 21 ? im.par : im.dpi;
+                const uint32_t pos = lane < 12 ? lane & 3u : lane < 17 ? 0u : (lane - 17u) & 3u;
+                uint32_t b = (word >> (24u - 8u * pos)) & 255u;
+                if (lane >= 12 && lane < 17) b = lane == 12 ? 1u : lane == 13 ? ch : lane == 14 ? 8u : lane == 15 ? im.cs : 0u;
+                reinterpret_cast<uint8_t*>(stage)[lane] = (uint8_t)b;
+            }
+            fill = 2 * kHeader;
+        } else {
+            dst += kHeader + (pl.off >> 1);
+            if (pl.off & 1u) {                                               // the byte shared with the segment in front is written here, whole
+                if (lane == 0) stage[0] = (pl.carry & 15u) << 4;
+                fill = 1;
+            }
+        }
+        wave_order();
+    } else ld = -1;
+    uint32_t top_n = 0, v_n = pixel(min(s0 + lane, total - 1), &top_n);
+    for (uint32_t i0 = s0; i0 < s1; i0 += kWave) {
+        const uint32_t v = v_n, top = top_n;
+        if (i0 + kWave < s1) v_n = pixel(min(i0 + kWave + lane, total - 1), &top_n);       // asked for while this group is encoded
+        const uint32_t i = i0 + lane;
+        const bool valid = i < s1;
+        uint32_t prev = __shfl_up(v, 1, kWave);
+        if (lane == 0) prev = last_v;
+        const bool diff = valid && v != prev;
+        const uint64_t D = __ballot(diff);
+        const uint64_t below = D & lt;
+        const bool known = seen || below;                                    // a pixel that differed lies in front, in this segment or (kWrite) by e
+        const uint32_t k = (uint32_t)((int32_t)i - (below ? (int32_t)i0 + (63 - __builtin_clzll(below)) : ld));
+        uint64_t nib = 0; uint32_t n = 0;
+        if (diff) {
+            const uint32_t pending = (k - 1) % kRunMax;                      // :254-255
+            if (known && pending) nib = qp_run(pending, &n);
+            uint32_t m;
+            const uint32_t op = qp_op(v, prev, top > 255u ? prev & 255u : top, &m);
+            nib |= (uint64_t)op << (4 * n); n += m;
+        } else if (valid && known) {                                         // :246-251
+            const uint32_t r = k % kRunMax;
+            if (r == 0) nib = qp_run(kRunMax, &n);
+            else if (i == total - 1) nib = qp_run(r, &n);
+        }
+        const uint64_t n0 = __ballot(n & 1u), n1 = __ballot(n & 2u), n2 = __ballot(n & 4u), n3 = __ballot(n & 8u);     // n <= 9
+        const uint32_t sum = (uint32_t)__builtin_popcountll(n0) + 2u * (uint32_t)__builtin_popcountll(n1) + 4u * (uint32_t)__builtin_popcountll(n2) +
+                             8u * (uint32_t)__builtin_popcountll(n3);
+        if (kWrite) {
+            uint32_t q = fill + (uint32_t)__builtin_popcountll(n0 & lt) + 2u * (uint32_t)__builtin_popcountll(n1 & lt) +
+                         4u * (uint32_t)__builtin_popcountll(n2 & lt) + 8u * (uint32_t)__builtin_popcountll(n3 & lt);
+            uint32_t cur = q >> 3, acc = 0;                                  // nibble q: byte q / 2, high half when q is even
+            for (uint32_t j = 0; j < n; ++j, ++q) {
+                if ((q >> 3) != cur) { atomicOr(&stage[cur], acc); acc = 0; cur = q >> 3; }
+                acc |= (uint32_t)((nib >> (4 * j)) & 15u) << (8u * ((q >> 1) & 3u) + ((q & 1u) ? 0u : 4u));
+            }
+            if (n) atomicOr(&stage[cur], acc);
+            fill += sum;
+            if (fill >= 2 * kQpFlushAt) {                                    // whole bytes leave; a half byte stays as the stage's first
+                const uint32_t bytes = fill >> 1, used = (fill + 7) >> 3;
+                wave_order(); flush_run<kWave>(stage, dst + written, bytes, lane); wave_order();
+                const uint32_t half = (fill & 1u) ? byte_of(stage, bytes) : 0u;
+                wave_order();
+                for (uint32_t d = lane; d < used; d += kWave) stage[d] = 0;
+                wave_order();
+                if (lane == 0) stage[0] = half;
+                wave_order();
+                written += bytes; fill &= 1u;
+            }
+        } else {
+            if (!seen) lead = D ? i0 - s0 + (uint32_t)__builtin_ctzll(D) : s1 - s0;
+            rest += sum;
+            const uint64_t any = __ballot(n != 0);
+            if (any) { const uint32_t j = 63 - (uint32_t)__builtin_clzll(any); rest_last = (uint32_t)(rdl((uint32_t)(nib >> (4 * (rdl(n, j) - 1))), j)) & 15u; }
+        }
+        if (D) { ld = (int32_t)i0 + (63 - __builtin_clzll(D)); seen = true; }
+        last_v = rdl(v, kWave - 1);
+    }
+    if (kWrite) {
+        if (holds_last) {                                                    // :313-317: nine f nibbles, one more to end on a byte
+            const uint32_t closing = 9 + ((fill + 9) & 1u), q = fill + lane;
+            wave_order();
+            if (lane < closing) atomicOr(&stage[q >> 3], 15u << (8u * ((q >> 1) & 3u) + ((q & 1u) ? 0u : 4u)));
+            fill += closing;
+        }
+        // a segment that emitted nothing writes nothing; one that ends on a half byte leaves it to the next that emits
+        wave_order();
+        flush_run<kWave>(stage, dst + written, fill >> 1, lane);
+    } else if (lane == 0) {
+        rec[qi.seg0 + seg] = QpSeg{ seen ? ld : -1, lead, rest, rest_last };
+    }
+}
+
+__global__ void __launch_bounds__(kWave) k_qpenc_count(const QpImg* __restrict__ imgs, int n_imgs, QpSeg* __restrict__ segs)
+{
+    const QpImg qi = imgs[find_unit<&QpImg::seg0>(imgs, n_imgs, blockIdx.x)];
+    qp_segment<false>(qi, blockIdx.x - qi.seg0, segs, nullptr, nullptr);
+}
+
+// A wave per image over its segments, 64 at a time: the run count that enters a segment is its distance to the last pixel that
+// differed (a prefix maximum) modulo 258; with it the leading stretch's nibbles are known, and a prefix sum gives every segment its
+// first nibble; the last nibble in front of it (a prefix "last one that exists") completes a shared byte.
+__global__ void __launch_bounds__(kWave) k_qpenc_scan(const QpImg* __restrict__ imgs, const QpSeg* __restrict__ segs, QpPlace* __restrict__ place,
+                                                     uint32_t* __restrict__ file_len)
+{
+    const QpImg qi = imgs[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+    int32_t run_ld = -1;
+    uint32_t run_off = 0, run_last = kNoNibble;
+    for (uint32_t base = 0; base < qi.nseg; base += kWave) {
+        const uint32_t s = base + lane;
+        const bool valid = s < qi.nseg;
+        const QpSeg rec = valid ? segs[qi.seg0 + s] : QpSeg{ -1, 0u, 0u, kNoNibble };
+        int32_t ldmax = rec.last_diff;
+        #pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) { const int32_t t = __shfl_up(ldmax, d, kWave); if ((int)lane >= d) ldmax = max(ldmax, t); }
+        int32_t before = __shfl_up(ldmax, 1, kWave);
+        before = lane == 0 ? run_ld : max(before, run_ld);
+        const uint32_t s0 = valid ? s * kSeg : 0u;
+        const uint32_t e = valid ? (uint32_t)((int32_t)s0 - 1 - before) % kRunMax : 0u;
+        uint32_t last;
+        uint32_t nib = qp_lead(e, rec.lead, rec.last_diff >= 0 || s + 1 == qi.nseg, &last);
+        if (rec.rest) last = rec.rest_last;
+        nib += rec.rest;
+        if (!valid) { nib = 0; last = kNoNibble; }
+        uint32_t sum = nib;
+        #pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const uint32_t t = __shfl_up(sum, d, kWave), tl = __shfl_up(last, d, kWave);
+            if ((int)lane >= d) { sum += t; if (last == kNoNibble) last = tl; }
+        }
+        uint32_t carry = __shfl_up(last, 1, kWave);
+        if (lane == 0 || carry == kNoNibble) carry = run_last;
+        if (valid) place[qi.seg0 + s] = QpPlace{ e, run_off + sum - nib, carry, 0u };
+        run_ld = max(run_ld, (int32_t)rdl((uint32_t)ldmax, kWave - 1));
+        run_off += rdl(sum, kWave - 1);
+        const uint32_t l63 = rdl(last, kWave - 1);
+        if (l63 != kNoNibble) run_last = l63;
+    }
+    const uint32_t nibbles = run_off + 9u + ((run_off + 9u) & 1u);
+    if (lane == 0) file_len[qi.im.slot] = kHeader + (nibbles >> 1);
+}
+
+__global__ void __launch_bounds__(kWave) k_qpenc_write(const QpImg* __restrict__ imgs, int n_imgs, const QpPlace* __restrict__ place)
+{
+    __shared__ uint32_t stage[kQpStageDwords];
+    const QpImg qi = imgs[find_unit<&QpImg::seg0>(imgs, n_imgs, blockIdx.x)];
+    qp_segment<true>(qi, blockIdx.x - qi.seg0, nullptr, place, stage);
+}
+
 // ---- LZ4_compress -----------------------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ uint32_t rd32(const uint8_t* p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
@@ -421,16 +682,27 @@ __global__ void __launch_bounds__(kPickThreads) k_qxenc_pick(const PickJob* __re
 
 int64_t lz4_bound(int64_t n) { return n < 0 || n > (int64_t)kLzMaxInput ? 0 : n + n / 255 + 16; }             // LZ4_COMPRESSBOUND
 
+// 1 and 2 channels are QOI-Plane and exist while the codec's switch is on (gamut_hip_qoix_set_plane)
 bool desc_ok(const gamut_hip_qoix_desc& d)
 {
-    return d.width > 0 && d.height > 0 && d.channels >= 3 && d.channels <= 4 && d.colorspace >= 0 && d.colorspace <= 2 &&
+    const bool channels_ok = (d.channels >= 3 && d.channels <= 4) || ((d.channels == 1 || d.channels == 2) && qoix_plane_on());
+    return d.width > 0 && d.height > 0 && channels_ok && d.colorspace >= 0 && d.colorspace <= 2 &&
            (d.mode == 0 || d.mode == 1) && (uint32_t)d.height < kPixelsMax / (uint32_t)d.width;
+}
+
+// the most bytes the stored stream behind the header can have: colour, a pixel's channels + 1 and the four closing bytes; grey, 3 or
+// 6 nibbles a pixel, the closing nine and one more to end on a byte (DEVIATION G1)
+int64_t datalen_max_of(const gamut_hip_qoix_desc& d)
+{
+    const int64_t px = (int64_t)d.width * d.height;
+    return d.channels >= 3 ? px * (d.channels + 1) + 4 : (px * (d.channels == 1 ? 3 : 6) + 10) / 2;
 }
 
 int64_t encode_bound(const gamut_hip_qoix_desc* d)
 {
     if (!d || !desc_ok(*d)) return -1;
-    const int64_t datalen_max = (int64_t)d->width * d->height * (d->channels + 1) + 4;
+    if (d->channels == 2 && (int64_t)d->width * d->height * 6 > 0x7fffffffLL) return -1;      // DEVIATION G2
+    const int64_t datalen_max = datalen_max_of(*d);
     const int64_t b = kHeader + 4 + datalen_max + datalen_max / 255 + 16;
     return b > 0x7fffffffLL ? -1 : b;                                        // DEVIATION 2
 }
@@ -440,6 +712,7 @@ uint32_t float_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 // Measurements (tools/qoix_encode_bench.py): with GAMUT_HIP_QOIX_TIMING=1 the encode call brackets its three launches with events and
 // keeps the GPU times of the calling thread's last call.
 thread_local float t_last_encode_stage_ms[3] = { -1.0f, -1.0f, -1.0f };
+thread_local float t_last_plane_stage_ms[3] = { -1.0f, -1.0f, -1.0f };       // k_qpenc_count, k_qpenc_scan, k_qpenc_write
 
 int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_qoix_desc* descs, int count, const int64_t* out_offset,
                  uint8_t* out, int64_t* out_len, int* status_host, hipStream_t stream)
@@ -460,7 +733,7 @@ int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamu
         im.slot = (uint32_t)imgs.size();
         size_t a = (size_t)-1, c = (size_t)-1;
         if (d.mode == 0) {                                                   // both candidates in scratch, congruent to the destination modulo 16
-            const size_t datalen_max = (size_t)d.width * d.height * (d.channels + 1) + 4, shift = (uintptr_t)im.dst & 15u;
+            const size_t datalen_max = (size_t)datalen_max_of(d), shift = (uintptr_t)im.dst & 15u;
             a = scratch + shift; scratch += up16(shift + kHeader + datalen_max) + 16;
             c = scratch + shift; scratch += up16(shift + kHeader + 4 + (size_t)lz4_bound((int64_t)datalen_max)) + 16;
         }
@@ -471,9 +744,16 @@ int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamu
         const size_t n = imgs.size();
         size_t nlz = 0;
         for (size_t k = 0; k < n; ++k) nlz += at_stored[k] != (size_t)-1;
-        const size_t o_img = 0, o_lz = up256(n * sizeof(QeImg)), o_pick = o_lz + up256(nlz * sizeof(LzJob) + 4), o_len = o_pick + up256(nlz * sizeof(PickJob) + 4),
+        size_t ngrey = 0, nsegs = 0;
+        for (size_t k = 0; k < n; ++k)
+            if (imgs[k].ch < 3) { ++ngrey; nsegs += ((size_t)imgs[k].w * imgs[k].h + kSeg - 1) / kSeg; }
+        if (nsegs > 0x7fffffffu) return set_error(GAMUT_HIP_ERR_INVALID_ARG, "qoix_encode: %zu segments of grey images in one call", nsegs);
+        const size_t ncol = n - ngrey;
+        const size_t o_img = 0, o_grey = up256(ncol * sizeof(QeImg) + 4), o_lz = o_grey + up256(ngrey * sizeof(QpImg) + 4),
+                     o_pick = o_lz + up256(nlz * sizeof(LzJob) + 4), o_len = o_pick + up256(nlz * sizeof(PickJob) + 4),
                      staged = o_len, o_lzlen = o_len + up256(n * 4), o_fin = o_lzlen + up256(n * 4), lens_end = o_fin + up256(n * 4),
-                     total = lens_end + scratch;
+                     o_seg = lens_end, o_place = o_seg + up256(nsegs * sizeof(QpSeg)), o_scratch = o_place + up256(nsegs * sizeof(QpPlace)),
+                     total = o_scratch + scratch;
         static thread_local PerDevice<DeviceScratch> scratch_pd;
         static thread_local PerDevice<PinnedScratch> pinned_pd;
         uint8_t* d = (uint8_t*)scratch_pd.cur().get(total, stream);
@@ -481,21 +761,37 @@ int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamu
         if (!d || !h) return set_error(GAMUT_HIP_ERR_OUT_OF_MEMORY, "qoix_encode: scratch allocation of %zu bytes failed", total);
         for (size_t k = 0; k < n; ++k) {
             if (at_stored[k] == (size_t)-1) continue;
-            uint8_t* stored = d + lens_end + at_stored[k];
-            uint8_t* cand = d + lens_end + at_cand[k];
+            uint8_t* stored = d + o_scratch + at_stored[k];
+            uint8_t* cand = d + o_scratch + at_cand[k];
             lzs.push_back(LzJob{ stored, cand, 0u, 1u, imgs[k].slot, 0u });
             picks.push_back(PickJob{ stored, cand, imgs[k].dst, imgs[k].slot, 0u });
             imgs[k].dst = stored;
         }
         memset(h, 0, staged);
-        memcpy(h + o_img, imgs.data(), n * sizeof(QeImg));
+        QeImg* colour = (QeImg*)(h + o_img); QpImg* grey = (QpImg*)(h + o_grey);
+        uint32_t seg0 = 0;
+        for (size_t k = 0; k < n; ++k) {
+            if (imgs[k].ch >= 3) { *colour++ = imgs[k]; continue; }
+            const uint32_t nseg = (uint32_t)(((size_t)imgs[k].w * imgs[k].h + kSeg - 1) / kSeg);
+            *grey++ = QpImg{ imgs[k], seg0, nseg };
+            seg0 += nseg;
+        }
         if (nlz) { memcpy(h + o_lz, lzs.data(), nlz * sizeof(LzJob)); memcpy(h + o_pick, picks.data(), nlz * sizeof(PickJob)); }
         GAMUT_HIP_CHECK(hipMemcpyAsync(d, h, staged, hipMemcpyHostToDevice, stream));
         uint32_t* d_len = (uint32_t*)(d + o_len); uint32_t* d_lz = (uint32_t*)(d + o_lzlen); uint32_t* d_fin = (uint32_t*)(d + o_fin);
         static const bool timing = env_flag("GAMUT_HIP_QOIX_TIMING");
-        KernelTimer<4> timer(timing);
+        KernelTimer<7> timer(timing);
         timer.mark(stream);
-        hipLaunchKernelGGL(k_qxenc_ops, dim3((uint32_t)n), dim3(kWave), 0, stream, (const QeImg*)(d + o_img), d_len);
+        if (ncol) hipLaunchKernelGGL(k_qxenc_ops, dim3((uint32_t)ncol), dim3(kWave), 0, stream, (const QeImg*)(d + o_img), d_len);
+        timer.mark(stream);
+        if (ngrey) {                                                         // three launches whatever the grey images are
+            const QpImg* d_grey = (const QpImg*)(d + o_grey);
+            hipLaunchKernelGGL(k_qpenc_count, dim3((uint32_t)nsegs), dim3(kWave), 0, stream, d_grey, (int)ngrey, (QpSeg*)(d + o_seg));
+            timer.mark(stream);
+            hipLaunchKernelGGL(k_qpenc_scan, dim3((uint32_t)ngrey), dim3(kWave), 0, stream, d_grey, (const QpSeg*)(d + o_seg), (QpPlace*)(d + o_place), d_len);
+            timer.mark(stream);
+            hipLaunchKernelGGL(k_qpenc_write, dim3((uint32_t)nsegs), dim3(kWave), 0, stream, d_grey, (int)ngrey, (const QpPlace*)(d + o_place));
+        } else { timer.mark(stream); timer.mark(stream); }
         timer.mark(stream);
         hipLaunchKernelGGL(k_qxenc_lz4, dim3((uint32_t)std::max<size_t>(nlz, 1)), dim3(kWave), 0, stream, (const LzJob*)(d + o_lz), (int)nlz,
                            (const uint32_t*)d_len, d_lz);
@@ -506,7 +802,12 @@ int encode_batch(const uint8_t* const* src, const int64_t* src_pitch, const gamu
         timer.mark(stream);
         GAMUT_HIP_CHECK(hipMemcpyAsync(h + o_len, d + o_len, lens_end - o_len, hipMemcpyDeviceToHost, stream));
         GAMUT_HIP_CHECK(hipStreamSynchronize(stream));
-        timer.finish(t_last_encode_stage_ms);
+        if (timing) {
+            float ms[6];
+            timer.finish(ms);
+            t_last_encode_stage_ms[0] = ms[0]; t_last_encode_stage_ms[1] = ms[4]; t_last_encode_stage_ms[2] = ms[5];
+            for (int k = 0; k < 3; ++k) t_last_plane_stage_ms[k] = ngrey ? ms[1 + k] : -1.0f;
+        }
         const uint32_t* stored_len = (const uint32_t*)(h + o_len); const uint32_t* fin = (const uint32_t*)(h + o_fin);
         for (size_t k = 0; k < n; ++k) out_len[which[k]] = at_stored[k] == (size_t)-1 ? stored_len[k] : fin[k];
     }
@@ -612,5 +913,9 @@ float gamut_hip_qoix_last_encode_kernel_ms(void)
 }
 
 float gamut_hip_qoix_last_encode_stage_ms(int stage) { return stage >= 0 && stage < 3 ? t_last_encode_stage_ms[stage] : -1.0f; }
+
+int gamut_hip_qoix_plane_encode_segment(void) { return (int)kSeg; }
+
+float gamut_hip_qoix_last_plane_encode_stage_ms(int stage) { return stage >= 0 && stage < 3 ? t_last_plane_stage_ms[stage] : -1.0f; }
 
 } // extern "C"

@@ -58,7 +58,7 @@ TO_GREYSCALE, TO_RGB, TO_ADD_ALPHA, TO_DROP_ALPHA, TO_PREMUL, TO_NO_PREMUL, TO_8
 LOAD_GREYSCALE, LOAD_ALPHA, LOAD_NO_ALPHA, LOAD_RGB = 0x10000, 0x20000, 0x40000, 0x80000
 LOAD_8BIT, LOAD_16BIT, LOAD_FP32, LOAD_PREMUL, LOAD_NO_PREMUL = 0x100000, 0x200000, 0x400000, 0x1000000, 0x2000000
 FORMAT_UNKNOWN, FORMAT_JPEG, FORMAT_PNG, FORMAT_QOI = -1, 0, 1, 2
-FORMAT_QOIX = 3                                                # ImageFormat.QOIX: 8-bit rgb / rgba files, read (loadFromMemory) and written (save_qoix_to_memory); save_to_memory(3) returns None
+FORMAT_QOIX = 3                                                # ImageFormat.QOIX: 8-bit rgb / rgba files (l / la too while the QOI-Plane switch is on), read (loadFromMemory) and written (save_qoix_to_memory); save_to_memory(3) returns None
 FORMAT_DDS = 4                                                 # ImageFormat.DDS: written only (save_dds_to_memory), as in the reference; save_to_memory(4) returns None
 FORMAT_GIF = 6                                                 # ImageFormat.GIF: every frame a layer, read and written (rgba8)
 FORMAT_TGA = 5                                                 # ImageFormat.TGA: read (loadFromMemory) and written (save_tga_to_memory); save_to_memory(5) returns None
@@ -224,7 +224,8 @@ class Image:
 
     def saveTGAToFile(self, path, flags=0): return bool(self.L.gamut_image_save_tga_to_file(self.h, str(path).encode(), flags))
 
-    # saveQOIX (plugins/qoix.d:156-242): rgb8 / rgba8 / rgbap8, layer 0, LZ4 when that is smaller; flags are ignored
+    # saveQOIX (plugins/qoix.d:156-242): rgb8 / rgba8 / rgbap8, and l8 / la8 / lap8 while the QOI-Plane switch is on (gamut_hip_qoix_set_plane,
+    # GAMUT_HIP_QOIX_PLANE=1; off they are refused); layer 0, LZ4 when that is smaller; flags are ignored
     def save_qoix_to_memory(self, flags=0):
         """the QOIX file as bytes, or None when the image is refused"""
         return self._encoded(self.L.gamut_image_save_qoix_to_memory, flags)

@@ -880,7 +880,8 @@ float gamut_hip_qoix_last_decode_stage_ms(int stage);
  * as it did before the codec existed.  On, 8-bit files with 1 or 2 channels decode through every QOIX entry and Image.loadFromMemory;
  * gamut_hip_qoix_decode_batch_device then also takes channels 1 / 2, which apply to grey files as 3 / 4 apply to colour files: a file
  * of the other family gets GAMUT_HIP_ERR_INVALID_ARG as its status, writes nothing and does not disturb its neighbours (channels 0
- * suits a mixed batch).  Grey files run in a third launch, k_qoix_plane (a wave each), skipped when the batch holds none. */
+ * suits a mixed batch).  Grey files run in a third launch, k_qoix_plane (a wave each), skipped when the batch holds none.
+ * The switch means "the QOI-Plane codec is on" in both directions: on, the encode entries below take channels 1 / 2 as well. */
 int   gamut_hip_qoix_set_plane(int on);
 /* k_qoix_plane keeps rows of up to this many pixels in LDS; a wider row lives in a global scratch row */
 int   gamut_hip_qoix_plane_row_capacity(void);
@@ -898,18 +899,28 @@ float gamut_hip_qoix_last_plane_kernel_ms(void);
  *   1. for 4 channels the reference copies pitchBytes into a scanline buffer of 4 * width bytes (a padded pitch overruns it, a
  *      negative one is a huge memcpy); here width * channels bytes of every row are read, whatever the pitch is;
  *   2. the reference's int max_size wraps for large shapes; a description whose bound exceeds 2^31 - 1 is refused instead.
- * Grey (1 or 2 channels) and the 10-bit codecs are not built: refused.
+ * Grey, 1 or 2 channels, is QOI-Plane (qoiplane_encode, codecs/qoiplane.d:109-365) and exists while gamut_hip_qoix_set_plane is on; off,
+ * such a description is refused as before the codec existed.  The state starts as {l: 0, a: 255}; a run is cut at 258 pixels, at the
+ * last pixel and in front of a pixel that differs (REPEAT1 for 1..3, REPEAT2 above); an alpha step outside -7..7 is an LA, one inside
+ * an ADIFF and a luminance op; the luminance op is the first of DIFF1, DIFF2, DIRECT that fits the difference to the rounded-up mean
+ * of the pixel above (row 0: the predecessor) and the predecessor; nine f nibbles close the stream, one more ends it on a byte.
+ * Colorspace 0..2 is written as given (saveQOIX writes 2 for lap8, which qoiplane_decode then refuses).  Deviations of the grey codec:
+ *   G1. the reference allocates (w * h * n + 1) / 2 + 29 bytes (n = 3 or 6 nibbles a pixel), a byte too few when every pixel takes
+ *       its worst op and w * h * n is even; the bound here is sized by the true maximum, datalen_max = (w * h * n + 10) / 2;
+ *   G2. w * h * 6 above 2^31 - 1 (2 channels, more than 357913941 pixels) is refused: the reference's int size wraps there.
+ * A batch may mix grey and colour images.  The 10-bit codecs are not built: refused.
  * (Declared typedef-first: the layout of this struct is pinned by tests/c/qoix_encode_abi_layout.c and tests/test_qoix_encode_cpu.py.) */
 typedef struct gamut_hip_qoix_desc gamut_hip_qoix_desc;
 struct gamut_hip_qoix_desc {
     int32_t width, height;
-    int32_t channels;               /* 3 | 4: the SOURCE's channel count, which is the file's */
+    int32_t channels;               /* 3 | 4, and 1 | 2 while gamut_hip_qoix_set_plane is on: the SOURCE's channel count, which is the file's */
     int32_t colorspace;             /* 0..2, header byte 15 (2: premultiplied alpha) */
     int32_t mode;                   /* 0: the reference's choice, LZ4 when lz4Size + 4 < datalen, else stored; 1: always stored (qoix_encode alone) */
     float   pixel_aspect_ratio;     /* header bytes 17..20, big-endian, bit for bit (NaN payloads included) */
     float   resolution_y;           /* header bytes 21..24, likewise */
 };
-/* the bytes a caller must provide for one file: with datalen_max = width * height * (channels + 1) + 4 it is
+/* the bytes a caller must provide for one file: with datalen_max = width * height * (channels + 1) + 4 (colour) or
+ * (width * height * n + 10) / 2, n = 3 nibbles a pixel for 1 channel and 6 for 2 (grey), it is
  * 29 + datalen_max + datalen_max / 255 + 16 (the stored file and the LZ4 file at LZ4_compressBound); -1 for a refused description
  * (NULL, the reference's refusals, a mode other than 0 / 1, a bound above 2^31 - 1) */
 int64_t gamut_hip_qoix_encode_bound(const gamut_hip_qoix_desc* desc);
@@ -918,7 +929,10 @@ int64_t gamut_hip_qoix_encode_bound(const gamut_hip_qoix_desc* desc);
  * outside [out_offset[i], out_offset[i] + out_len[i]) is written.  out_len[i] / status_host[i] (host arrays; status_host may be
  * NULL) are filled when the call returns: a refused image (or a NULL src[i], a negative out_offset[i]) gets
  * GAMUT_HIP_ERR_INVALID_ARG and out_len 0, the others are still encoded, and the call returns the status of the lowest-numbered
- * refused image ("image %d:" in last_error).  Three launches, whatever the batch holds: ops, LZ4, the choice. */
+ * refused image ("image %d:" in last_error).  Three launches, whatever a batch of colour images holds: ops, LZ4, the choice.  Grey
+ * images add three of their own, whatever they are -- k_qpenc_count and k_qpenc_write, a wave per segment of
+ * gamut_hip_qoix_plane_encode_segment() pixels of the raster, and k_qpenc_scan between them -- and a batch without colour images
+ * does not launch the colour op kernel. */
 int     gamut_hip_qoix_encode_batch_device(const uint8_t* const* src, const int64_t* src_pitch, const gamut_hip_qoix_desc* descs, int count,
                                            const int64_t* out_offset, uint8_t* out, int64_t* out_len, int* status_host, void* stream);
 /* host drop-in for qoix_lz4_encode: host pixels (rows `pitch` bytes apart, negative allowed) through pinned staging -> malloc'd file
@@ -926,6 +940,8 @@ int     gamut_hip_qoix_encode_batch_device(const uint8_t* const* src, const int6
 void*   gamut_hip_qoix_write_to_mem(const void* data, int pitch, const gamut_hip_qoix_desc* desc, int* out_len);
 /* the op kernel takes this many pixels of the raster per step */
 int     gamut_hip_qoix_encode_window(void);
+/* the grey encoder cuts an image's raster into segments of this many consecutive pixels (a multiple of 64, whatever the width is) */
+int     gamut_hip_qoix_plane_encode_segment(void);
 /* LZ4_compressBound (n + n / 255 + 16; 0 for n < 0 or n > 0x7E000000), and LZ4_compress for `count` byte strings in DEVICE memory:
  * string i (src[i], len[i] bytes, any alignment) becomes the LZ4 block at out + out_offset[i], which must have
  * gamut_hip_lz4_compress_bound(len[i]) bytes; out_len[i] is the block's length, byte for byte what LZ4_compress writes on a 64-bit
@@ -938,6 +954,9 @@ int     gamut_hip_lz4_compress_batch_device(const uint8_t* const* src, const int
  * all three launches, or one of them (0 ops, 1 LZ4, 2 the choice); -1 when timing is off or nothing was encoded */
 float   gamut_hip_qoix_last_encode_kernel_ms(void);
 float   gamut_hip_qoix_last_encode_stage_ms(int stage);
+/* likewise the grey encoder's three launches in the calling thread's last encode call (0 count, 1 scan, 2 write); -1 when timing is
+ * off or that call encoded no grey image.  The getters above do not include them. */
+float   gamut_hip_qoix_last_plane_encode_stage_ms(int stage);
 
 /* ---- files of any of the three formats, one call ---------------------------------------------------------------------
  * The reference loads any file through Image.loadFromMemory: identifyFormatFromStream (image.d:1045-1061 -- the plugins' detect
